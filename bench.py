@@ -10,9 +10,12 @@ slabs they consume, as the reference does) and rotates over 4 output pictures, s
 runs on cached or already-zeroed data.  N > 1: frame-parallel replicas, one frame stream
 per GPU, no data-path collective ("weak" scaling).
 
-Prints ONE JSON line (rank 0) with the throughput, the roofline of the dominant kernel
-(measured live with HIP events on the launch stream) and the CPU baseline (the oracle
-replayed on the host cores for a bounded number of frames).
+A plain run sets up, warms up, times the steps, writes the last step's pictures when
+--dump-outputs DIR is given, and prints ONE JSON line (rank 0) with the throughput and
+ms_per_step.  --full adds everything else the benchmark measures or checks: the parity gate
+against the oracle, the roofline of the dominant kernel (measured live with HIP events on the
+launch stream), the CPU baseline (the oracle replayed on the host cores for a bounded number
+of frames), the other layouts, precisions, sizes and legs, and with N > 1 the C3 / C4 legs.
 """
 import argparse
 import ctypes as C
@@ -64,7 +67,7 @@ def parse():
     ap.add_argument("--e2e-threads", type=int, default=64, help="listing threads (of the library, dav1d_hip_lister_run) of the one-frame-at-a-time end-to-end legs (0: one per tile).  The MI355X boxes of this pool give the container 16 cores' worth of CPU time per 100 ms (cgroup cpu.max): a burst on 64 threads runs at full speed until that is spent, then every thread stops for the rest of the period — the frames-in-flight legs report both ways")
     ap.add_argument("--stream-frames", type=int, default=25, help="frames of the AV1 stream of the dav1d_task_loop_real_pass1 leg (every one compared with dav1d's)")
     ap.add_argument("--no-c1", action="store_true", help="skip the 4K 8-bit (BASELINE configs[1]) line that the default run appends")
-    ap.add_argument("--no-full", action="store_true", help="skip the full-DSP-table leg (deblock, CDEF, restoration, film grain)")
+    ap.add_argument("--no-full", action="store_true", help="with --full: skip the full-DSP-table leg (deblock, CDEF, restoration, film grain)")
     ap.add_argument("--two-phase", action="store_true",
                     help="run the step as dav1d_hip_inter_list_run + dav1d_hip_itx_list_run (every residual after every prediction) "
                          "instead of the pipelined dav1d_hip_recon_list_run")
@@ -88,12 +91,41 @@ def parse():
                     help="CPU run on the SIMT-emulated build of the same kernel sources (tests/emu), torch.distributed over gloo: what "
                          "tests/test_dist.py uses to run `bench.py --gpus 2` without a GPU (tiny sizes; no timing means anything)")
     ap.add_argument("--one-leg", action="store_true",
-                    help="N > 1: only the leg the other flags select (default: three legs in one line — frame-parallel replicas, tile columns "
-                         "with in-loop filters (C3), dependent frames with film grain (C4))")
+                    help="N > 1 with --full: only the leg the other flags select (default there: three legs in one line — frame-parallel replicas, "
+                         "tile columns with in-loop filters (C3), dependent frames with film grain (C4)); without --full only that leg runs anyway")
     ap.add_argument("--tc-filters", action="store_true",
                     help="tile-cols only: the step also runs deblocking, CDEF and loop restoration of the rank's column after a halo "
                          "exchange of 16 luma columns with its neighbours (dav1d_amd/dist.py), and gathers the FILTERED columns")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else: parity against the oracle, per-kernel roofline and counted traffic, CPU "
+                         "baselines, the other layouts, the packed format, the full-table, end-to-end and task-loop legs, the 4K 8-bit lines, "
+                         "and with N > 1 the C3 / C4 legs (the --no-* flags above trim this).  Off: the headline step alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the pictures the last timed step produced (rank 0) as DIR/<name>.npy, float32, visible area only; %d samples "
+                         "at most in all: a plane above its share is cut to a fixed, seeded sample of whole rows (sorted)" % DUMP_SAMPLES)
     return ap.parse_args()
+
+
+DUMP_SAMPLES = 15 << 20         # float32: 60 MiB in all, under 64 MB
+
+
+def dump_outputs(out_dir, planes):
+    """planes: [(name, 2-D array of pixel values)] -> out_dir/<name>.npy as float32 (pixels of up to 16 bits are exact).  A plane
+    above its share of DUMP_SAMPLES keeps a seeded choice of whole rows, the same rows for the same plane shape in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_SAMPLES // len(planes)
+    for name, p in planes:
+        p = np.asarray(p)
+        if p.size > share:
+            n_rows = max(1, share // p.shape[1])
+            rows = np.sort(np.random.default_rng(0xD0C5 + p.shape[0] * 65536 + p.shape[1]).choice(p.shape[0], n_rows, replace=False))
+            p = p[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(p, dtype=np.float32))
+
+
+def visible(planes, w, h):
+    """the picture area of the three (padded) planes of a 4:2:0 picture"""
+    return [pl[:h, :w] if k == 0 else pl[:(h + 1) >> 1, :(w + 1) >> 1] for k, pl in enumerate(planes)]
 
 
 def algorithmic_bytes(frame):
@@ -509,7 +541,7 @@ def main():
         t = torch.ones(1, dtype=torch.int32, device=DEV(a))
         dist.all_reduce(t)                       # RCCL (gloo with --emu): how many ranks really take part
         ranks_seen = int(t.item())
-    if world > 1 and not a.one_leg and a.shard == "frames" and a.config == "c2" and not a.step_only:
+    if world > 1 and a.full and not a.one_leg and a.shard == "frames" and a.config == "c2" and not a.step_only:
         # ---- three legs in one line: replicas (the headline step on every GPU), C3, C4
         import copy
         primary = run_job(a, rank, local, world)
@@ -548,7 +580,11 @@ def main():
         line = run_job(a, rank, local, world)
         if rank == 0 and line is not None:
             line["n_ranks_seen"] = ranks_seen
-            emit(line)
+            if a.full or a.step_only:
+                emit(line)
+            else:               # a plain run: the headline line alone
+                print(json.dumps(line))
+                sys.stdout.flush()
     if world > 1:
         dist.barrier()
         dd.close_peers()
@@ -622,7 +658,7 @@ def run_job(a, rank, local, world):
             wl.step(arenas[i].data_ptr())
         torch.cuda.synchronize()
         parity = "skipped"
-        if rank == 0 and not a.no_check and a.dependent and a.warmup:
+        if rank == 0 and a.full and not a.no_check and a.dependent and a.warmup:
             # the chain so far (every rank runs the same frame, reference 0 = what rank - 1 restored one step earlier) against the
             # oracle's replay of the same number of steps
             import util
@@ -652,7 +688,11 @@ def run_job(a, rank, local, world):
         torch.cuda.synchronize()
         dd.barrier(world)
         dt = dd.max_over_ranks(time.perf_counter() - t0, world, device=dev)
-        if rank == 0 and not a.no_check and not a.dependent:
+        if rank == 0 and a.dump_outputs:
+            got_res, got_grn = wl.outputs()
+            dump_outputs(a.dump_outputs, [("restored_" + c, p) for c, p in zip("yuv", visible(got_res, w, h))] +
+                         [("grain_" + c, p) for c, p in zip("yuv", visible(got_grn, w, h))])
+        if rank == 0 and a.full and not a.no_check and not a.dependent:
             # this rank's last frame against the oracle's replay of the same lists (independent frames: every step gives the same picture)
             import util
             import test_frame
@@ -729,6 +769,11 @@ def run_job(a, rank, local, world):
     tdt = torch.int16 if bpc == 8 else torch.int32
     pristine = torch.from_numpy(coef_host).to(dev)
     n_arena = a.steps + a.warmup + 8
+    if not a.packed and not a.emu:
+        # at most half the free device memory for the arenas: a smaller pool is refilled (untimed) whenever its arenas are all consumed,
+        # and the timed steps run in chunks of what is left fresh (one chunk whenever the whole run fits, as the default does)
+        fit = int(torch.cuda.mem_get_info()[0] * 0.5) // (pristine.numel() * pristine.element_size())
+        n_arena = min(n_arena, max(a.warmup + 16, fit))
     if a.packed:        # a packed arena is read-only: every step reads the same one
         arenas = [pristine] * n_arena
     else:
@@ -738,7 +783,7 @@ def run_job(a, rank, local, world):
     torch.cuda.synchronize()
     # what the boundary costs when the residuals arrive from the host every frame (reported next to `value`, never in it)
     h2d_ms = None
-    if rank == 0 and not a.emu:
+    if rank == 0 and a.full and not a.emu:
         pinned = torch.from_numpy(coef_host).pin_memory()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         best = 1e9
@@ -765,13 +810,13 @@ def run_job(a, rank, local, world):
         d = dsts[i % NDST]
         if recon_list is not None and tiled:
             _, rl_k, prep_k, _ = lanes[i % n_fc]
-            rl_k.run_tiled(d, refs, prep_k.data_ptr(), arenas[i].data_ptr())
+            rl_k.run_tiled(d, refs, prep_k.data_ptr(), arenas[i % n_arena].data_ptr())
         elif recon_list is not None:
             _, rl_k, prep_k, _ = lanes[i % n_fc]
-            rl_k.run(d, refs, prep_k.data_ptr(), arenas[i].data_ptr())
+            rl_k.run(d, refs, prep_k.data_ptr(), arenas[i % n_arena].data_ptr())
         else:
             ctx.run_inter_list(inter_list, d, refs, prep.data_ptr())
-            ctx.run_itx_list(itx_list, d, arenas[i].data_ptr())
+            ctx.run_itx_list(itx_list, d, arenas[i % n_arena].data_ptr())
         if tile_cols and tc_post is not None:
             dd.exchange_halo(d, cols, rank, world)       # enqueued on the context's stream behind the reconstruction (dav1d_hip_peer_exchange_halo)
             pa, cdf, res = tc_post["all"], tc_post["cdf"], tc_post["res"]
@@ -802,23 +847,51 @@ def run_job(a, rank, local, world):
 
     barrier()
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(a.warmup, a.warmup + a.steps):
-        step(i)
-    torch.cuda.synchronize()
-    barrier()
-    dt = time.perf_counter() - t0
+    dt, i, fresh = 0.0, a.warmup, n_arena - a.warmup
+    while i < a.warmup + a.steps:
+        if not fresh:
+            for k in range(n_arena):
+                arenas[k].copy_(pristine)
+            torch.cuda.synchronize()
+            barrier()
+            fresh = n_arena
+        j = min(a.warmup + a.steps, i + fresh)
+        t0 = time.perf_counter()
+        for k in range(i, j):
+            step(k)
+        torch.cuda.synchronize()
+        barrier()
+        dt += time.perf_counter() - t0
+        fresh -= j - i
+        i = j
     dt = dd.max_over_ranks(dt, world, device=dev)
 
     ms_per_step = dt / a.steps * 1e3
     # whole-job luma Mpixels/s: N frames per step (one per GPU) when sharded by frame, ONE frame per step over tile columns
     value = (whole.luma_pixels * a.steps / dt if tile_cols else dd.job_throughput(frame.luma_pixels, a.steps, dt, world)) / 1e6
+    if rank == 0 and a.dump_outputs:
+        last = final_pic[0] if tc_post is not None else dsts[(a.warmup + a.steps - 1) % NDST]
+        dump_outputs(a.dump_outputs, [("picture_" + c, p) for c, p in zip("yuv", visible([last.download(pl) for pl in range(3)], w, h))])
+    label = "8K" if (w, h) == (7680, 4320) else "4K" if (w, h) == (3840, 2160) else "%dx%d" % (w, h)
+    metric = "reconstructed luma Mpixels/s (%s 4:2:0 %d-bit) on the itx+mc recon path; bit-exact vs C" % (label, bpc)
+    scaling = "strong" if tile_cols else "weak"
 
     # ---- the same step fed with the sparse coefficient format (DAV1D_HIP_ITX_PACKED): reported next to `value`, which keeps
     # the dense reference layout SURVEY 8d prices; rank 0 of a one-GPU run only, and checked against the same oracle pictures
     if a.step_only:
         barrier()
         return {"step_only": True, "ms_per_step": round(ms_per_step, 4), "value": round(value, 1), "steps": a.steps, "warmup": a.warmup} if rank == 0 else None
+    if not a.full:
+        barrier()
+        return {"metric": metric, "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+                "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+                "dtype": "int32" if bpc > 8 else "int16", "data": "synthetic",
+                "config": {"frame_contexts": n_fc, "picture_layout": "tiled" if tiled else "raster", "parity": "not checked in this run (bench.py --full checks it)"},
+                "roofline": None, "cpu_baseline": None} if rank == 0 else None
+    if n_arena < a.warmup + a.steps + 8 and not a.packed:       # the legs below take arenas from the start of the pool again
+        for k in range(n_arena):
+            arenas[k].copy_(pristine)
+        torch.cuda.synchronize()
     packed_leg = None
     if rank == 0 and world == 1 and not a.packed and not a.two_phase:
         p_tasks, p_coef = synth.pack_frame_coefs(frame)
@@ -842,7 +915,8 @@ def run_job(a, rank, local, world):
     # ---- the same step with the pictures laid out the other ways, same box, same run (reported, never `value`): raster planes throughout
     # (the reference's layout, rounds 1-4) and raster destination + tiled references
     by_layout = None
-    if rank == 0 and world == 1 and tiled and recon_list is not None and not a.packed and not a.emu and not os.environ.get("DAV1D_BENCH_CHILD"):
+    if rank == 0 and world == 1 and tiled and recon_list is not None and not a.packed and not a.emu and not os.environ.get("DAV1D_BENCH_CHILD") \
+            and n_arena >= a.warmup + a.steps:
         by_layout = {"tiled": round(ms_per_step, 4)}
         alt = [ctx.picture(w, h, api.LAYOUT_I420, bpc) for _ in range(2)]
         for d in alt:
@@ -882,7 +956,7 @@ def run_job(a, rank, local, world):
             rc = ctx.lib.dav1d_hip_inter_list_run_timed(ctx.h, inter_list.h, C.byref(d.pic), rarr, len(refs), prep.data_ptr(), None,
                                                         ms_mc, cnt_mc)
             assert rc == 0
-            rc = ctx.lib.dav1d_hip_itx_list_run_timed(ctx.h, itx_list.h, C.byref(d.pic), arenas[i + rep].data_ptr(), ms_itx, cnt_itx)
+            rc = ctx.lib.dav1d_hip_itx_list_run_timed(ctx.h, itx_list.h, C.byref(d.pic), arenas[(i + rep) % n_arena].data_ptr(), ms_itx, cnt_itx)
             assert rc == 0
             torch.cuda.synchronize()
             best_mc = [min(x, y) for x, y in zip(best_mc, ms_mc)]
@@ -924,7 +998,7 @@ def run_job(a, rank, local, world):
             for rep in range(3):
                 rarr = (api.Picture * len(refs))(*[r.pic for r in refs])
                 fn = ctx.lib.dav1d_hip_recon_list_run_tiled_timed if tiled else ctx.lib.dav1d_hip_recon_list_run_timed
-                rc = fn(ctx.h, recon_list.h, C.byref(d.pic), rarr, len(refs), prep.data_ptr(), None, arenas[i + 3 + rep].data_ptr(), ms40, cnt40)
+                rc = fn(ctx.h, recon_list.h, C.byref(d.pic), rarr, len(refs), prep.data_ptr(), None, arenas[(i + 3 + rep) % n_arena].data_ptr(), ms40, cnt40)
                 assert rc == 0, rc
                 best40 = [min(x, y) for x, y in zip(best40, ms40)]
             step_kernels = []
@@ -1046,7 +1120,7 @@ def run_job(a, rank, local, world):
             elif not a.no_check:
                 got = [dsts[i % NDST].download(pl) for pl in range(3)]
                 ok = all(np.array_equal(got[pl], want[0][pl]) for pl in range(3))
-                ok = ok and (a.packed or not bool(arenas[i].any().item()))
+                ok = ok and (a.packed or not bool(arenas[i % n_arena].any().item()))
                 check = "bit-exact vs %s oracle (3 planes of the last frame)" % oracle.which if ok else "MISMATCH"
                 if not ok:
                     raise SystemExit("bench: GPU output differs from the oracle")
@@ -1448,10 +1522,9 @@ def run_job(a, rank, local, world):
                 cpu["all_cores_value"], cpu["all_cores_cores"] = cpu["all_cores"].get("value"), cpu["all_cores"].get("cores")
             if isinstance(cpu.get("reference_pass2"), dict) and "value" in cpu["reference_pass2"]:
                 cpu["reference_pass2_value"], cpu["reference_pass2_cores"] = cpu["reference_pass2"]["value"], cpu["reference_pass2"]["cores"]
-        label = "8K" if (w, h) == (7680, 4320) else "4K" if (w, h) == (3840, 2160) else "%dx%d" % (w, h)
-        out = {"metric": "reconstructed luma Mpixels/s (%s 4:2:0 %d-bit) on the itx+mc recon path; bit-exact vs C" % (label, bpc),
+        out = {"metric": metric,
                "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-               "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong" if tile_cols else "weak", "vs_baseline": None,
+               "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
                "dtype": "int32" if bpc > 8 else "int16", "data": "synthetic",
                "config": {"workload": ("%dx%d 4:2:0 %d-bit inter frame, itx+mc recon (SURVEY §8d C1 spec: every block 16x16, TX_16X16 luma / TX_8X8 "
                                        "chroma, single reference, all blocks coded, 3 refs); lists resident in HBM" if a.mix == "c1" else
@@ -1478,7 +1551,7 @@ def run_job(a, rank, local, world):
             import subprocess
             for key, mix in (("config_c1_4k_8bit", "c1"), ("config_c1_4k_8bit_c2_mix", "c2")):
                 try:
-                    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--width", "3840", "--height", "2160", "--bpc", "8", "--no-c1", "--mix", mix,
+                    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--width", "3840", "--height", "2160", "--bpc", "8", "--no-c1", "--mix", mix,
                                             "--no-full", "--no-e2e", "--no-cpu", "--steps", str(a.steps), "--warmup", str(a.warmup)],
                                            capture_output=True, text=True, timeout=600)
                     cj = json.loads(child.stdout.strip().splitlines()[-1])

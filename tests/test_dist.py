@@ -425,7 +425,7 @@ def test_bench_py_starts_its_own_launcher_and_reports_three_legs_world2_gloo():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--emu", "--width", "256", "--height", "128",
-                        "--steps", "2", "--warmup", "2", "--cpu-seconds", "0.1"], capture_output=True, text=True, env=env, timeout=1500, cwd="/tmp")
+                        "--steps", "2", "--warmup", "2", "--cpu-seconds", "0.1", "--full"], capture_output=True, text=True, env=env, timeout=1500, cwd="/tmp")
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -452,7 +452,7 @@ def test_bench_py_n_gpus_runs_dav1ds_loop_over_the_devices_of_one_process_world2
         env.pop(k, None)
     env["DAV1D_BENCH_N_DEVICES_LEG"] = "1"
     r = subprocess.run([sys.executable, os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--emu", "--width", "256", "--height", "128",
-                        "--steps", "2", "--warmup", "2", "--cpu-seconds", "0.1"], capture_output=True, text=True, env=env, timeout=1500, cwd="/tmp")
+                        "--steps", "2", "--warmup", "2", "--cpu-seconds", "0.1", "--full"], capture_output=True, text=True, env=env, timeout=1500, cwd="/tmp")
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 8000, lines

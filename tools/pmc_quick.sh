@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "$@"; do
     i=$((i+1))
-    timeout 150 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/pmc$i" -- python "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu --no-check > "$OUT/pmc$i.log" 2>&1
+    timeout 150 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/pmc$i" -- python "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-check > "$OUT/pmc$i.log" 2>&1
 done
 python - <<PY
 import csv, glob, collections

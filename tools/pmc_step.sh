@@ -10,7 +10,7 @@ export DAV1D_HIP_SERIAL=1
 i=0
 for grp in "$@"; do
     i=$((i+1))
-    timeout 150 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/pmc$i" -- python "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu --no-check --no-full --no-e2e --no-c1 > "$OUT/pmc$i.log" 2>&1 || echo "pass $i ($grp) failed: $(tail -2 $OUT/pmc$i.log)"
+    timeout 150 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/pmc$i" -- python "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-check --no-full --no-e2e --no-c1 > "$OUT/pmc$i.log" 2>&1 || echo "pass $i ($grp) failed: $(tail -2 $OUT/pmc$i.log)"
 done
 python - <<PY
 import csv, glob, collections
