@@ -10,8 +10,11 @@ import numpy as np
 from . import _lib
 from ._lib import FilmGrainData  # noqa: F401
 from ._lib import ITX_TASK, MC_TASK, COMP_TASK, CDEF_TASK, LF_TASK, IPRED_TASK, LR_TASK, WARP_TASK, MC_SCALED_TASK, Picture, HostPicture  # noqa: F401  (re-exported)
+from ._lib import Surface as SurfaceDesc
 
 LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
+SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR = 0, 1, 2      # enum Dav1dHipSurfaceFormat
+SAMPLE_NATIVE, SAMPLE_MSB16, SAMPLE_F32 = 0, 1, 2                     # enum Dav1dHipSurfaceSample
 
 
 class HipError(RuntimeError):
@@ -114,6 +117,11 @@ class DevicePicture:
                                                    out.strides[0], 1), "plane_download")
         return out
 
+    def export(self, surface, row0=0, row1=1 << 30):
+        """dav1d_hip_surface_export: luma rows [row0, row1) of this picture into a device surface of the caller, on the context's stream
+        (asynchronous; a picture that lives in its twin only is read through the twin and stays there)."""
+        _chk(self.ctx.lib.dav1d_hip_surface_export(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), row0, row1), "surface_export")
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -127,6 +135,104 @@ class DevicePicture:
     def free(self):
         if not getattr(self, "borrowed", False):
             self.ctx.lib.dav1d_hip_picture_free(self.ctx.h, C.byref(self.pic))
+
+
+def surface_planes(w, h, layout, bpc, fmt, sample):
+    """[(rows, samples per row)] of the planes of a surface, and the numpy dtype of its samples (include/dav1d_hip.h, Dav1dHipSurface)."""
+    dt = np.dtype(np.float32 if sample == SAMPLE_F32 else np.uint16 if sample == SAMPLE_MSB16 or bpc > 8 else np.uint8)
+    if fmt == SURFACE_RGB_PLANAR:
+        return [(h, w)] * 3, dt
+    if layout == LAYOUT_I400:
+        return [(h, w)], dt
+    cw = (w + 1) >> 1 if layout != LAYOUT_I444 else w
+    ch = (h + 1) >> 1 if layout == LAYOUT_I420 else h
+    if fmt == SURFACE_SEMIPLANAR:
+        return [(h, w), (ch, 2 * cw)], dt
+    return [(h, w), (ch, cw), (ch, cw)], dt
+
+
+class Surface:
+    """A Dav1dHipSurface: device memory a picture is exported into (DevicePicture.export).  Context.surface() makes one that owns its
+    buffers; Surface.wrap() describes memory of somebody else (a torch tensor, an encoder's input) and frees nothing."""
+
+    def __init__(self, ctx, w, h, layout, bpc, fmt, sample, matrix=1, full_range=0, strides=None):
+        self.ctx = ctx
+        self.shapes, self.dtype = surface_planes(w, h, layout, bpc, fmt, sample)
+        self.strides = list(strides) if strides is not None else [cols * self.dtype.itemsize for _, cols in self.shapes]
+        assert len(self.strides) == len(self.shapes)
+        self.bufs = [ctx.buffer(max(rows * st, 16)) for (rows, _), st in zip(self.shapes, self.strides)]
+        self._describe([b.ptr for b in self.bufs], w, h, fmt, sample, matrix, full_range)
+
+    def _describe(self, ptrs, w, h, fmt, sample, matrix, full_range):
+        self.desc = SurfaceDesc()
+        for k, p in enumerate(ptrs):
+            self.desc.data[k] = p
+            self.desc.stride[k] = self.strides[k]
+        self.desc.format, self.desc.sample, self.desc.w, self.desc.h = fmt, sample, w, h
+        self.desc.matrix, self.desc.full_range = matrix, full_range
+
+    @classmethod
+    def wrap(cls, ctx, ptrs, strides, w, h, layout, bpc, fmt, sample, matrix=1, full_range=0):
+        """Foreign device memory: ptrs / strides (bytes) per plane of the format."""
+        self = cls.__new__(cls)
+        self.ctx, self.bufs = ctx, None
+        self.shapes, self.dtype = surface_planes(w, h, layout, bpc, fmt, sample)
+        self.strides = list(strides)
+        self._describe(list(ptrs), w, h, fmt, sample, matrix, full_range)
+        return self
+
+    def fill(self, byte):
+        for b in self.bufs:
+            _chk(self.ctx.lib.dav1d_hip_memset(self.ctx.h, b.ptr, byte, b.nbytes), "memset")
+
+    def raw(self, k):
+        """every byte of plane k's buffer as (rows, stride) uint8 (waits for the context's stream)"""
+        rows = self.shapes[k][0]
+        return self.bufs[k].download(np.uint8, rows * self.strides[k]).reshape(rows, self.strides[k])
+
+    def download(self):
+        """numpy arrays of the visible size, one per plane of the format"""
+        out = []
+        for k, (rows, cols) in enumerate(self.shapes):
+            out.append(np.ascontiguousarray(self.raw(k)[:, :cols * self.dtype.itemsize]).view(self.dtype))
+        return out
+
+    def free(self):
+        for b in self.bufs or []:
+            b.free()
+        self.bufs = None
+
+
+def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30):
+    """Fills torch tensors on the picture's device through tensor.data_ptr(): `tensor` of shape (3, h, w) gets R, G, B planes; with
+    `chroma` of shape (ceil(h / 2), 2 * ceil(w / 2)) given, `tensor` (h, w) gets luma and `chroma` the interleaved U, V of a 4:2:0
+    picture (NV12 / P010 family).  The sample type follows the dtype (float32: F32; else `sample`, native by default).  The context should
+    have been opened on the stream the tensors are used on (api.Context(stream=torch.cuda.current_stream().cuda_stream))."""
+    import torch
+    ts = [tensor] if chroma is None else [tensor, chroma]
+    for t in ts:
+        if not t.is_cuda or t.stride(-1) != 1:
+            raise ValueError("export_to_tensor needs device tensors with unit stride along a row")
+    if sample is None:
+        sample = SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_NATIVE
+    es = tensor.element_size()
+    if chroma is None:
+        if tuple(tensor.shape) != (3, pic.h, pic.w):
+            raise ValueError("an RGB tensor has shape (3, h, w)")
+        fmt = SURFACE_RGB_PLANAR
+        ptrs = [tensor[k].data_ptr() for k in range(3)]
+        strides = [tensor.stride(1) * es] * 3
+    else:
+        if tuple(tensor.shape) != (pic.h, pic.w) or chroma.dtype != tensor.dtype:
+            raise ValueError("a semi-planar pair has shapes (h, w) and (ceil(h / 2), 2 * ceil(w / 2)) and one dtype")
+        fmt = SURFACE_SEMIPLANAR
+        ptrs = [tensor.data_ptr(), chroma.data_ptr()]
+        strides = [tensor.stride(0) * es, chroma.stride(0) * es]
+    s = Surface.wrap(pic.ctx, ptrs, strides, pic.w, pic.h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
+    if s.dtype.itemsize != es or [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]:
+        raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
+    pic.export(s, row0, row1)
+    return s
 
 
 class _List:
@@ -248,6 +354,10 @@ class Context:
 
     def picture(self, w, h, layout, bpc):
         return DevicePicture(self, w, h, layout, bpc)
+
+    def surface(self, w, h, layout, bpc, format, sample, matrix=1, full_range=0, strides=None):
+        """A device output surface that owns its buffers (dav1d_hip_malloc); strides in bytes per plane, tight rows by default."""
+        return Surface(self, w, h, layout, bpc, format, sample, matrix, full_range, strides)
 
     def graph_begin(self):
         """Start recording the list runs issued on this context (dav1d_hip_graph_begin)."""

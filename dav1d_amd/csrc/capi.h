@@ -53,6 +53,7 @@ struct Dav1dHipContext {
     // measurement aid: device time of the kernel launches of the most recent *_batch call (dav1d_hip_last_kernel_ms)
     hipEvent_t ev_t0, ev_t1;
     float last_ms;
+    bool last_ms_pending;       // ev_t0 / ev_t1 bracket a call that returned without waiting (dav1d_hip_surface_export): last_ms is read from them on demand
     // chunked frames (chunk.hip): pinned slabs recycled between frames, the device arenas of the frame in flight, a copy stream
     struct Slab { uint8_t *host; size_t cap; };
     std::mutex pool_mtx;
@@ -126,6 +127,7 @@ struct KernelTimer {
         (void) hipEventRecord(c->ev_t1, c->stream);
         (void) hipEventSynchronize(c->ev_t1);
         c->last_ms = 0.f;
+        c->last_ms_pending = false;
         (void) hipEventElapsedTime(&c->last_ms, c->ev_t0, c->ev_t1);
     }
 };

@@ -136,6 +136,7 @@ int dav1d_hip_open(Dav1dHipContext **out, int device, void *stream) {
     if (hipEventCreateWithFlags(&c->ev_retile, hipEventDisableTiming) != hipSuccess) { delete c; return -ENODEV; }
     c->retile_pending = false;
     c->last_ms = 0.f;
+    c->last_ms_pending = false;
     c->gather_dev = c->segtab_dev = c->pending_slab = nullptr;
     c->gather_cap = c->segtab_cap = c->pending_slab_cap = 0;
     c->arena_hint = 0;
@@ -276,7 +277,15 @@ int dav1d_hip_set_option(Dav1dHipContext *c, const char *name, long value) {
 }
 
 const char *dav1d_hip_version(void) { return "dav1d_hip 0.1 (gfx950)"; }
-float dav1d_hip_last_kernel_ms(Dav1dHipContext *c) { return c ? c->last_ms : 0.f; }
+float dav1d_hip_last_kernel_ms(Dav1dHipContext *c) {
+    if (!c) return 0.f;
+    if (c->last_ms_pending) {           // the call that recorded the events did not wait for them (dav1d_hip_surface_export)
+        c->last_ms_pending = false;
+        c->last_ms = 0.f;
+        if (hipEventSynchronize(c->ev_t1) == hipSuccess) (void) hipEventElapsedTime(&c->last_ms, c->ev_t0, c->ev_t1);
+    }
+    return c->last_ms;
+}
 
 int dav1d_hip_malloc(Dav1dHipContext *c, void **dev, size_t bytes) {
     (void) c;

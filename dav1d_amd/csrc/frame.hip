@@ -371,7 +371,7 @@ static int post_filters_pipelined(Dav1dHipFrame *f, const Dav1dHipPicture **last
         if (b + 1 < nb) f->publish(final_rows[b], out_pic);         // the last band is published with the frame (frame_run)
     }
     (void) hipStreamSynchronize(c->stream);
-    if (!rc) { c->last_ms = 0.f; (void) hipEventElapsedTime(&c->last_ms, c->ev_t0, c->ev_t1); }
+    if (!rc) { c->last_ms = 0.f; c->last_ms_pending = false; (void) hipEventElapsedTime(&c->last_ms, c->ev_t0, c->ev_t1); }
     for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
     *last_out = has_lr ? &f->tmp[1] : cdef_out;
     if (!rc) f->post_bands = nb;

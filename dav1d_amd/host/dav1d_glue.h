@@ -98,6 +98,10 @@ void dav1d_hip_glue_filter_desc(Dav1dHipFilterDesc *fd, const Dav1dFrameContext 
 /* ---- output: film grain on the device for a picture dav1d_get_picture handed out (Dav1dSettings.apply_grain = 0 with the backend:
  * dav1d_apply_grain, src/lib.c:311-329, reads host planes).  Tight rows into dst[pl] (row pitch = plane width in bytes). */
 int dav1d_hip_glue_output_with_grain(Dav1dHipGlue *g, const Dav1dPicture *pic, uint8_t *const dst[3]);
+/* ---- output that stays on the device: the picture into a surface of the caller (Dav1dHipSurface: planar, NV12 / P010 family, RGB planes; device
+ * memory on the device the picture's pixels live on), with its film grain when apply_grain is set and the frame header carries any.  dst->matrix and
+ * dst->full_range are the caller's; pic->seq_hdr->mtrx and pic->seq_hdr->color_range are the usual source.  Returns when the surface is written. */
+int dav1d_hip_glue_output_surface(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, int apply_grain);
 
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *g);    /* frames that failed INSIDE the backend (not: frames dav1d rejects) */
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *g);

@@ -215,6 +215,37 @@ DAV1D_HIP_API int dav1d_hip_host_picture_alloc(Dav1dHipContext *c, Dav1dHipHostP
 DAV1D_HIP_API int dav1d_hip_host_picture_release(Dav1dHipContext *c, Dav1dHipHostPicture *hp);
 DAV1D_HIP_API int dav1d_hip_host_picture_fetch(Dav1dHipContext *c, const Dav1dHipHostPicture *hp, const Dav1dHipPicture *src, int row0, int row1);
 DAV1D_HIP_API int dav1d_hip_host_picture_wait(Dav1dHipContext *c);
+/* ---- output on the device.  A decoded picture leaves the library for a consumer on the SAME device (a tensor pipeline, an encoder, a scaler) as a
+ * surface the caller owns: tight planar planes, a semi-planar NV12 / P010-family surface, or RGB planes.  dav1d_hip_surface_export reads the picture where
+ * it lives — the raster planes, or the tiled twin of a picture with twin_ok == DAV1D_HIP_TWIN_ONLY, which is NOT un-tiled first: `src` is const and
+ * stays what it was — and writes luma rows [row0, row1) and the chroma rows under them (clamped to the picture like dav1d_hip_host_picture_fetch; both
+ * multiples of 2 unless they are the picture's end, so an application can export band by band as dav1d_hip_frame_set_progress_callback reports rows).
+ * One launch on the context's stream; the call returns at once, dav1d_hip_sync waits, dav1d_hip_last_kernel_ms reports its device time.  Only visible
+ * pixels are written: nothing right of `w` samples of a row, nothing outside the rows, nothing in a plane the format does not have.
+ * RGB is integer arithmetic (DESIGN.md 10 has the formula; dav1d_amd/csrc/surface.hip the table): chroma is replicated, luma (x, y) takes chroma
+ * (x >> ss_hor, y >> ss_ver); I400 takes cb = cr = 0; matrix 0 (identity, 4:4:4 only) copies G = Y, B = U, R = V.
+ * -EINVAL, before anything is enqueued: a null plane the format needs, w / h that differ from the picture's, a stride below the row's bytes or not a
+ * multiple of the sample size, MSB16 at 8 bpc, matrix 0 with a layout other than 4:4:4, an odd row0 (or an odd row1 above the picture's end);
+ * -ENOTSUP: any other matrix code; -EXDEV: a source picture of another device than the context's. */
+enum Dav1dHipSurfaceFormat {
+    DAV1D_HIP_SURFACE_PLANAR     = 0,  /* data[0..2] = Y, U, V (I400: Y only) */
+    DAV1D_HIP_SURFACE_SEMIPLANAR = 1,  /* data[0] = Y, data[1] = U,V interleaved (NV12 / P010 family; I400: Y only) */
+    DAV1D_HIP_SURFACE_RGB_PLANAR = 2,  /* data[0..2] = R, G, B, each at luma size */
+};
+enum Dav1dHipSurfaceSample {
+    DAV1D_HIP_SAMPLE_NATIVE = 0,       /* uint8 at 8 bpc, uint16 with the value in the LOW bits at 10 / 12 bpc */
+    DAV1D_HIP_SAMPLE_MSB16  = 1,       /* uint16, value << (16 - bpc): P010 / P012 / P210 / P410; 8 bpc: -EINVAL */
+    DAV1D_HIP_SAMPLE_F32    = 2,       /* float, (float) value * (1.0f / ((1 << bpc) - 1)): one float multiply */
+};
+typedef struct Dav1dHipSurface {
+    void *data[3];        /* DEVICE memory of the caller (dav1d_hip_malloc, a torch tensor, ...) on the context's device */
+    ptrdiff_t stride[3];  /* bytes; any multiple of the sample size >= the row's bytes (tight rows included) */
+    int format, sample;   /* enum Dav1dHipSurfaceFormat, enum Dav1dHipSurfaceSample */
+    int w, h;             /* must equal the picture's visible luma size */
+    int matrix;           /* RGB only: AV1 matrix_coefficients (0 identity, 1 BT.709, 5 / 6 BT.601, 9 BT.2020 NCL) */
+    int full_range;       /* RGB only: color_range */
+} Dav1dHipSurface;
+DAV1D_HIP_API int dav1d_hip_surface_export(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, int row0, int row1);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

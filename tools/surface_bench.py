@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
+does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
+
+    python tools/surface_bench.py [--short] [--pairs 4] [--calls 200] [--repeats 3]
+
+N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
+Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
+everything repeated `repeats` times to show the spread.  Bytes per call come from the shapes (bytes read + bytes written).  The host
+fetch (dav1d_hip_host_picture_fetch + _wait) is printed for orientation only: it crosses PCIe and is no peer of a device-to-device pass.
+Needs the GPU; there is no fallback."""
+import argparse
+import ctypes as C
+import os
+import socket
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dav1d_amd import api  # noqa: E402
+
+SPEC_TBS, COPY_TBS = 8.0, 6.3         # HBM3E peak (spec) and the copy ceiling measured on the MI355X
+
+
+class Events:
+    def __init__(self, stream):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.stream = C.c_void_p(stream)
+        self.a, self.b = C.c_void_p(), C.c_void_p()
+        for e in (self.a, self.b):
+            assert self.hip.hipEventCreate(C.byref(e)) == 0
+
+    def start(self):
+        assert self.hip.hipEventRecord(self.a, self.stream) == 0
+
+    def stop_ms(self):
+        assert self.hip.hipEventRecord(self.b, self.stream) == 0
+        assert self.hip.hipEventSynchronize(self.b) == 0
+        ms = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.a, self.b) == 0
+        return ms.value
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
+    ap.add_argument("--pairs", type=int, default=4)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--width", type=int, default=7680)
+    ap.add_argument("--height", type=int, default=4320)
+    a = ap.parse_args()
+    if a.short:
+        a.calls, a.repeats = 40, 1
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    ctx = api.Context(0)
+    ev = Events(ctx.lib.dav1d_hip_stream(ctx.h))
+    rng = np.random.default_rng(1)
+    pics = []
+    for _ in range(a.pairs):
+        p = ctx.picture(w, h, layout, bpc)
+        for pl in range(3):
+            shape = p.padded_shape(pl)
+            p.upload(pl, rng.integers(0, 1 << bpc, size=shape, dtype=np.uint16))
+        p.retile()
+        p.pic.twin_ok = api.TWIN_ONLY
+        pics.append(p)
+    ctx.sync()
+    src_bytes = 2 * (w * h + 2 * cw * ch)
+    P, S, R = api.SURFACE_PLANAR, api.SURFACE_SEMIPLANAR, api.SURFACE_RGB_PLANAR
+    variants = [("planar native", P, api.SAMPLE_NATIVE, src_bytes), ("P010 (semi-planar MSB16)", S, api.SAMPLE_MSB16, src_bytes),
+                ("RGB planar native BT.709 limited", R, api.SAMPLE_NATIVE, 3 * 2 * w * h), ("RGB planar float32 BT.709 limited", R, api.SAMPLE_F32, 3 * 4 * w * h)]
+    if a.short:
+        variants = variants[:3]
+    runs = []
+    for name, fmt, sample, out_bytes in variants:
+        surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
+
+        def export(k, surfs=surfs):
+            p = pics[k % a.pairs]
+            p.pic.twin_ok = api.TWIN_ONLY      # (the yardstick's untile leaves 1: the twin is still the picture, and it is what gets read)
+            p.export(surfs[k % a.pairs])
+        runs.append((name, src_bytes + out_bytes, surfs, export))
+
+    def untile(k):
+        p = pics[k % a.pairs]
+        p.pic.twin_ok = api.TWIN_ONLY          # (untile leaves 1; the twin is still the picture)
+        p.untile()
+    # untile writes whole padded rows of the allocation: count what it moves
+    up = pics[0]
+    untile_bytes = 2 * sum(up.pic.p[pl].stride * (((up.pic.p[pl].h + 7) // 8) * 8) for pl in range(3))
+    runs.insert(0, ("dav1d_hip_picture_untile (yardstick)", untile_bytes, None, untile))
+
+    print("# surface_bench on %s: %dx%d 4:2:0 %d-bit, %d picture / surface pairs in rotation, 20 warm-up + %d timed calls per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, a.pairs, a.calls, a.repeats))
+    print("# bytes per call = bytes read + bytes written, from the shapes; share of %.1f TB/s (spec) and of the %.1f TB/s copy ceiling" % (SPEC_TBS, COPY_TBS))
+    results = {name: [] for name, _, _, _ in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, _, call in runs:
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            gbs = nbytes / ms / 1e6
+            print("repeat %d  %-40s %8.4f ms/call  %7.1f MB/call  %7.0f GB/s  %5.1f %% of spec  %5.1f %% of copy ceiling"
+                  % (rep, name, ms, nbytes / 1e6, gbs, gbs / (SPEC_TBS * 10), gbs / (COPY_TBS * 10)))
+    print("# summary (min / median / max ms per call over the repeats)")
+    for name, nbytes, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-40s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    u = sorted(results[runs[0][0]])
+    spread = u[-1] - u[0]
+    for name in (runs[1][0], runs[2][0]):
+        v = sorted(results[name])
+        print("condition %-40s median %.4f ms <= untile median %.4f ms + its spread %.4f ms: %s"
+              % (name, v[len(v) // 2], u[len(u) // 2], spread, "met" if v[len(v) // 2] <= u[len(u) // 2] + spread else "NOT met"))
+    # orientation only: the way out that exists without this call (host fetch: crosses PCIe, not a fair peer)
+    hp = api.HostPictureBuf(ctx, w, h, layout, bpc)
+    n = 3 if a.short else 10
+    for k in range(2):
+        hp.fetch(pics[k % a.pairs].pic)
+        hp.wait()
+    t0 = time.perf_counter()
+    for k in range(n):
+        hp.fetch(pics[k % a.pairs].pic)
+        hp.wait()
+    ms = (time.perf_counter() - t0) * 1e3 / n
+    print("orientation only, NOT a peer (device to host over PCIe): dav1d_hip_host_picture_fetch + _wait  %8.3f ms/picture (host clock, %d calls)" % (ms, n))
+    hp.release()
+    for _, _, surfs, _ in runs:
+        for s in surfs or []:
+            s.free()
+    for p in pics:
+        p.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
