@@ -316,6 +316,11 @@ int dav1d_hip_download(Dav1dHipContext *c, void *host, const void *dev, size_t b
 
 // ----------------------------------------------------------------- pictures
 
+// Entry points that write (or read and write) the RASTER planes of `dst` refuse a picture that lives in its tiled twin only
+// (DAV1D_HIP_TWIN_ONLY): they would work on stale planes and leave the flag saying that the twin is the picture.  -EINVAL before anything is
+// enqueued; the caller un-tiles first (dav1d_hip_picture_untile) or writes through dav1d_hip_recon_list_run_tiled.
+static inline bool raster_dst_ok(const Dav1dHipPicture *dst) { return dst && dst->twin_ok != DAV1D_HIP_TWIN_ONLY; }
+
 int dav1d_hip_picture_alloc(Dav1dHipContext *c, Dav1dHipPicture *pic, int w, int h, int layout, int bpc) {
     if (!pic || w <= 0 || h <= 0 || (bpc != 8 && bpc != 10 && bpc != 12) || layout < 0 || layout > 3)
         return -EINVAL;
@@ -856,7 +861,7 @@ void dav1d_hip_itx_list_destroy(Dav1dHipContext *c, Dav1dHipItxList *l) {
 }
 
 int dav1d_hip_itx_list_run(Dav1dHipContext *c, const Dav1dHipItxList *l, const Dav1dHipPicture *dst, void *coef) {
-    if (!l || !dst) return -EINVAL;
+    if (!l || !raster_dst_ok(dst)) return -EINVAL;
     const DevPlanes dp = dev_planes(dst);
     // longest-running shapes first (64-point, then 32-point ...), each on its own side stream
     static const uint8_t order[19] = { 4, 11, 12, 17, 18, 3, 9, 10, 15, 16, 2, 7, 8, 13, 14, 1, 5, 6, 0 };
@@ -876,7 +881,10 @@ int dav1d_hip_itx_list_run(Dav1dHipContext *c, const Dav1dHipItxList *l, const D
 }
 
 // Same launches, each bracketed by HIP events on the context's stream; ms[b] receives the
-// duration of bin b's kernel (0 for empty bins).  Measurement aid for bench.py.
+// duration of bin b's kernel (0 for empty bins).  Measurement aid for bench.py.  The *_timed aids of the itx, mc and inter lists (not dav1d_hip_recon_list_run_timed,
+// which is guarded like the run it times) take
+// `dst` as somewhere to write: they run on the raster planes of a picture in any state and leave twin_ok alone (bench.py times them on
+// the pictures of its tiled steps); what they leave in the raster planes of a DAV1D_HIP_TWIN_ONLY picture is not the picture.
 int dav1d_hip_itx_list_run_timed(Dav1dHipContext *c, const Dav1dHipItxList *l, const Dav1dHipPicture *dst, void *coef,
                                  float *ms, size_t *counts) {
     if (!l || !dst || !ms) return -EINVAL;
@@ -899,6 +907,7 @@ int dav1d_hip_itx_list_run_timed(Dav1dHipContext *c, const Dav1dHipItxList *l, c
 
 int dav1d_hip_itx_add_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipItxTask *tasks,
                             size_t n, void *coef) {
+    if (!raster_dst_ok(dst)) return -EINVAL;
     Dav1dHipItxList *l = nullptr;
     int rc = dav1d_hip_itx_list_create(c, &l, tasks, n);
     if (rc) return rc;
@@ -1135,7 +1144,7 @@ void dav1d_hip_mc_list_destroy(Dav1dHipContext *c, Dav1dHipMcList *l) {
 
 int dav1d_hip_mc_list_run(Dav1dHipContext *c, const Dav1dHipMcList *l, const Dav1dHipPicture *dst,
                           const Dav1dHipPicture *refs, int n_refs, int16_t *prep) {
-    if (!l || !dst || !refs || n_refs < 1 || n_refs > 8 || (l->n && l->max_ref >= n_refs)) return -EINVAL;
+    if (!l || !raster_dst_ok(dst) || !refs || n_refs < 1 || n_refs > 8 || (l->n && l->max_ref >= n_refs)) return -EINVAL;
     const DevPlanes dp = dev_planes(dst);
     DevPlanes rp[8];
     for (int i = 0; i < n_refs; i++) if (refs[i].bpc != dst->bpc) return -EINVAL;
@@ -1182,6 +1191,7 @@ int dav1d_hip_mc_list_run_timed(Dav1dHipContext *c, const Dav1dHipMcList *l, con
 
 int dav1d_hip_mc_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *refs, int n_refs,
                        const Dav1dHipMcTask *tasks, size_t n, int16_t *prep) {
+    if (!raster_dst_ok(dst)) return -EINVAL;
     Dav1dHipMcList *l = nullptr;
     int rc = dav1d_hip_mc_list_create(c, &l, tasks, n);
     if (rc) return rc;
@@ -1241,17 +1251,22 @@ void dav1d_hip_comp_list_destroy(Dav1dHipContext *c, Dav1dHipCompList *l) {
     delete l;
 }
 
-int dav1d_hip_comp_list_run(Dav1dHipContext *c, const Dav1dHipCompList *l, const Dav1dHipPicture *dst,
-                            const int16_t *prep, uint8_t *mask) {
-    if (!l || !dst) return -EINVAL;
+static int comp_list_launch(Dav1dHipContext *c, const Dav1dHipCompList *l, const Dav1dHipPicture *dst, const int16_t *prep, uint8_t *mask) {
     const DevPlanes dp = dev_planes(dst);
     int rc = dav1d_hip_launch_comp(&dp, dst->bpc, l->dev, (int) l->n_first, prep, mask, c->stream);
     if (!rc) rc = dav1d_hip_launch_comp(&dp, dst->bpc, l->dev + l->n_first, (int) (l->n - l->n_first), prep, mask, c->stream);
     return rc;
 }
 
+int dav1d_hip_comp_list_run(Dav1dHipContext *c, const Dav1dHipCompList *l, const Dav1dHipPicture *dst,
+                            const int16_t *prep, uint8_t *mask) {
+    if (!l || !raster_dst_ok(dst)) return -EINVAL;
+    return comp_list_launch(c, l, dst, prep, mask);
+}
+
 int dav1d_hip_comp_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipCompTask *tasks, size_t n,
                          const int16_t *prep, uint8_t *mask) {
+    if (!raster_dst_ok(dst)) return -EINVAL;
     Dav1dHipCompList *l = nullptr;
     int rc = dav1d_hip_comp_list_create(c, &l, tasks, n);
     if (rc) return rc;
@@ -1434,7 +1449,7 @@ void dav1d_hip_inter_list_destroy(Dav1dHipContext *c, Dav1dHipInterList *l) {
 
 int dav1d_hip_inter_list_run(Dav1dHipContext *c, const Dav1dHipInterList *l, const Dav1dHipPicture *dst,
                              const Dav1dHipPicture *refs, int n_refs, int16_t *prep, uint8_t *mask) {
-    if (!l) return -EINVAL;
+    if (!l || !raster_dst_ok(dst)) return -EINVAL;
     int rc = dav1d_hip_mc_list_run(c, l->mc, dst, refs, n_refs, prep);
     if (!rc && l->comp->n) rc = dav1d_hip_comp_list_run(c, l->comp, dst, prep, mask);
     return rc;
@@ -1451,7 +1466,7 @@ int dav1d_hip_inter_list_run_timed(Dav1dHipContext *c, const Dav1dHipInterList *
         hipEvent_t e0, e1;
         hipEventCreate(&e0); hipEventCreate(&e1);
         hipEventRecord(e0, c->stream);
-        rc = dav1d_hip_comp_list_run(c, l->comp, dst, prep, mask);
+        rc = comp_list_launch(c, l->comp, dst, prep, mask);
         hipEventRecord(e1, c->stream);
         hipStreamSynchronize(c->stream);
         hipEventElapsedTime(&ms[MC_BINS], e0, e1);
@@ -1468,13 +1483,14 @@ size_t dav1d_hip_inter_list_fused(const Dav1dHipInterList *l) { return l ? l->n_
 
 int dav1d_hip_cdef_run_groups(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *src, const Dav1dHipCdefTask *tasks,
                               size_t n, const CdefGroup *groups, size_t n_groups, size_t n_raw, int damping, uint32_t *dirvar) {
+    if (!raster_dst_ok(dst)) return -EINVAL;
+    if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;      // (a source that lives in its tiled twin only: raster planes first)
     const size_t tb = (n * sizeof(Dav1dHipCdefTask) + 255) & ~(size_t) 255;
     TaskBuf dev_buf(c, tb + n_groups * sizeof(CdefGroup) + 256);
     uint8_t *const dev = reinterpret_cast<uint8_t *>(dev_buf.p);
     if (!dev) return -ENOMEM;
     int rc = dav1d_hip_upload(c, dev, tasks, n * sizeof(Dav1dHipCdefTask));
     if (!rc && n_groups) rc = dav1d_hip_upload(c, dev + tb, groups, n_groups * sizeof(CdefGroup));
-    if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;      // (a source that lives in its tiled twin only: raster planes first)
     const DevPlanes dp = dev_planes(dst), sp = dev_planes(src);
     const Dav1dHipCdefTask *d_tasks = reinterpret_cast<const Dav1dHipCdefTask *>(dev);
     KernelTimer kt(c);
@@ -1488,7 +1504,7 @@ int dav1d_hip_cdef_run_groups(Dav1dHipContext *c, const Dav1dHipPicture *dst, co
 
 extern "C" int dav1d_hip_cdef_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *src,
                                     const Dav1dHipCdefTask *tasks, size_t n, int damping, uint32_t *dirvar) {
-    if (!dst || !src || (!tasks && n) || dst->bpc != src->bpc || dst->layout != src->layout) return -EINVAL;
+    if (!raster_dst_ok(dst) || !src || (!tasks && n) || dst->bpc != src->bpc || dst->layout != src->layout) return -EINVAL;
     if (!n) return 0;
     // one pass over the list (half a million units per 8K frame): the field checks as one OR-reduction
     unsigned bad = 0;
@@ -1518,7 +1534,7 @@ extern "C" int dav1d_hip_cdef_batch(Dav1dHipContext *c, const Dav1dHipPicture *d
 
 extern "C" int dav1d_hip_lf_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipLfTask *tasks, size_t n,
                                   const uint8_t *lvl, ptrdiff_t b4_stride, const uint8_t lut_e[64], const uint8_t lut_i[64]) {
-    if (!dst || (!tasks && n) || !lvl || !lut_e || !lut_i) return -EINVAL;
+    if (!raster_dst_ok(dst) || (!tasks && n) || !lvl || !lut_e || !lut_i) return -EINVAL;
     if (!n) return 0;
     std::vector<Dav1dHipLfTask> sorted;
     sorted.reserve(n);
@@ -1574,7 +1590,7 @@ static size_t ipred_big_first(Dav1dHipIpredTask *t, size_t n) {
 
 extern "C" int dav1d_hip_ipred_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipIpredTask *tasks, size_t n,
                                      uint8_t *pal_idx) {
-    if (!dst || (!tasks && n)) return -EINVAL;
+    if (!raster_dst_ok(dst) || (!tasks && n)) return -EINVAL;
     if (!n) return 0;
     if (ipred_tasks_valid(tasks, n, pal_idx)) return -EINVAL;
     std::vector<Dav1dHipIpredTask> ordered(tasks, tasks + n);
@@ -1633,7 +1649,7 @@ extern "C" int dav1d_hip_ipred_list_create(Dav1dHipContext *c, Dav1dHipIpredList
 // tmp: the scratch (prep) arena PRED_TMP tasks write to; NULL when the list holds none
 static int ipred_list_run_batch_tmp(Dav1dHipContext *c, const Dav1dHipIpredList *l, size_t batch, const Dav1dHipPicture *dst, uint8_t *aux,
                                     void *tmp) {
-    if (!l || !dst || batch + 1 >= l->start.size() || (l->needs_aux && !aux) || (l->needs_tmp && !tmp)) return -EINVAL;
+    if (!l || !raster_dst_ok(dst) || batch + 1 >= l->start.size() || (l->needs_aux && !aux) || (l->needs_tmp && !tmp)) return -EINVAL;
     const size_t n = l->start[batch + 1] - l->start[batch];
     if (!n) return 0;
     const DevPlanes dp = dev_planes(dst);
@@ -1667,7 +1683,7 @@ static int run_task_batch(Dav1dHipContext *c, const T *tasks, size_t n, Launch l
 
 extern "C" int dav1d_hip_warp_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *refs, int n_refs,
                                     const Dav1dHipWarpTask *tasks, size_t n, int16_t *prep) {
-    if (!dst || !refs || n_refs < 1 || n_refs > 8 || (!tasks && n)) return -EINVAL;
+    if (!raster_dst_ok(dst) || !refs || n_refs < 1 || n_refs > 8 || (!tasks && n)) return -EINVAL;
     if (!n) return 0;
     for (size_t i = 0; i < n; i++) {
         const Dav1dHipWarpTask &t = tasks[i];
@@ -1684,7 +1700,7 @@ extern "C" int dav1d_hip_warp_batch(Dav1dHipContext *c, const Dav1dHipPicture *d
 
 extern "C" int dav1d_hip_mc_scaled_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *refs, int n_refs,
                                          const Dav1dHipMcScaledTask *tasks, size_t n, int16_t *prep) {
-    if (!dst || !refs || n_refs < 1 || n_refs > 8 || (!tasks && n)) return -EINVAL;
+    if (!raster_dst_ok(dst) || !refs || n_refs < 1 || n_refs > 8 || (!tasks && n)) return -EINVAL;
     if (!n) return 0;
     for (size_t i = 0; i < n; i++) {
         const Dav1dHipMcScaledTask &t = tasks[i];
@@ -1703,7 +1719,7 @@ extern "C" int dav1d_hip_mc_scaled_batch(Dav1dHipContext *c, const Dav1dHipPictu
 
 extern "C" int dav1d_hip_resize(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *src, int plane, int dst_w, int y0,
                                 int h, int src_w, int dx, int mx0) {
-    if (!dst || !src || dst->bpc != src->bpc || plane < 0 || plane > 2 || dst_w < 1 || src_w < 1 || h < 0 || y0 < 0) return -EINVAL;
+    if (!raster_dst_ok(dst) || !src || dst->bpc != src->bpc || plane < 0 || plane > 2 || dst_w < 1 || src_w < 1 || h < 0 || y0 < 0) return -EINVAL;
     if (mx0 < 0 || mx0 > 0x3fff || dx < 0) return -EINVAL;
     if (!h) return 0;
     if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;      // (a source that lives in its tiled twin only: raster planes first)
@@ -1727,13 +1743,16 @@ extern "C" int dav1d_hip_emu_edge(Dav1dHipContext *c, int bpc, intptr_t bw, intp
 
 extern "C" int dav1d_hip_lr_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *src,
                                   const Dav1dHipPicture *lpf, const Dav1dHipLrTask *tasks, size_t n) {
-    if (!dst || !src || !lpf || (!tasks && n) || dst->bpc != src->bpc || lpf->bpc != src->bpc) return -EINVAL;
+    if (!raster_dst_ok(dst) || !src || !lpf || (!tasks && n) || dst->bpc != src->bpc || lpf->bpc != src->bpc) return -EINVAL;
     if (!n) return 0;
     for (size_t i = 0; i < n; i++) {
         const Dav1dHipLrTask &t = tasks[i];
         if (t.plane > 2 || t.edges > 15 || !t.w || t.w > 384 || !t.h || t.h > 64) return -EINVAL;
         if (t.type > DAV1D_HIP_LR_SGR_MIX) return -EINVAL;
     }
+    // (a source or a row store that lives in its tiled twin only: raster planes first, before anything is uploaded)
+    if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;
+    if (const int rv_ = raster_planes_valid(c, lpf, 1)) return rv_;
     // Wiener tasks first, self-guided tasks second: one launch each (tasks write disjoint stripes)
     std::vector<Dav1dHipLrTask> sorted;
     sorted.reserve(n);
@@ -1750,7 +1769,6 @@ extern "C" int dav1d_hip_lr_batch(Dav1dHipContext *c, const Dav1dHipPicture *dst
     Dav1dHipLrTask *const dev = reinterpret_cast<Dav1dHipLrTask *>(devb);
     int rc = dav1d_hip_upload(c, dev, sorted.data(), n * sizeof(*dev));
     if (!rc && !waves.empty()) rc = dav1d_hip_upload(c, devb + o_waves, waves.data(), waves.size() * 4);
-    if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;
     const DevPlanes dp = dev_planes(dst), sp = dev_planes(src), lp = dev_planes(lpf);
     KernelTimer kt(c);
     int max_w = 0;
@@ -1859,6 +1877,8 @@ static int fg_apply_core(Dav1dHipContext *c, const Dav1dHipPicture *dst, const D
                          uint8_t *offs) {
     const Dav1dHipFilmGrainData *data = &g->data;
     const int bpc = src->bpc;
+    // (a source that lives in its tiled twin only: raster planes first — the plane copies below read them as the kernel does)
+    if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;
     int rc = 0;
     // planes that get no grain are copied (dav1d_prep_grain, src/fg_apply_tmpl.c:127-163)
     const int ss_ver = src->layout == DAV1D_HIP_LAYOUT_I420;
@@ -1871,7 +1891,6 @@ static int fg_apply_core(Dav1dHipContext *c, const Dav1dHipPicture *dst, const D
         rc = hip_rc(hipMemcpy2DAsync(dst->p[pl].data, dst->p[pl].stride, src->p[pl].data, src->p[pl].stride, rb, rows,
                                      hipMemcpyDeviceToDevice, c->stream));
     }
-    if (const int rv_ = raster_planes_valid(c, src, 1)) return rv_;      // (a source that lives in its tiled twin only: raster planes first)
     const DevPlanes dp = dev_planes(dst), sp = dev_planes(src);
     if (!rc) rc = dav1d_hip_launch_fg_apply(&dp, &sp, (const int16_t *) g->dev, g->dev + g->lut_bytes, (int) g->scaling_size, data, bpc, src->layout,
                                             is_id, offs, c->stream);
@@ -1879,7 +1898,7 @@ static int fg_apply_core(Dav1dHipContext *c, const Dav1dHipPicture *dst, const D
 }
 
 static int fg_args_ok(const Dav1dHipPicture *dst, const Dav1dHipPicture *src) {
-    return dst && src && dst->bpc == src->bpc && dst->layout == src->layout;
+    return raster_dst_ok(dst) && src && dst->bpc == src->bpc && dst->layout == src->layout;
 }
 
 extern "C" int dav1d_hip_fg_apply_prepared(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *src,
@@ -2063,6 +2082,7 @@ static int recon_list_run_impl(Dav1dHipContext *c, const Dav1dHipReconList *l, c
 
 int dav1d_hip_recon_list_run(Dav1dHipContext *c, const Dav1dHipReconList *l, const Dav1dHipPicture *dst,
                              const Dav1dHipPicture *refs, int n_refs, int16_t *prep, uint8_t *mask, void *coef) {
+    if (!raster_dst_ok(dst)) return -EINVAL;
     return recon_list_run_impl(c, l, dst, refs, n_refs, prep, mask, coef, false, nullptr);
 }
 
@@ -2088,6 +2108,9 @@ int dav1d_hip_recon_list_run_twin(Dav1dHipContext *c, const Dav1dHipReconList *l
                                   const Dav1dHipPicture *refs, int n_refs, int16_t *prep, uint8_t *mask, void *coef) {
     if (!c || !l || !dst || !refs) return -EINVAL;
     if (!dst->twin[0] && !dst->twin_alloc) { const int rc = dav1d_hip_picture_twin_alloc(c, dst); if (rc) return rc; }
+    // (the launches write raster planes: a picture that lives in its twin gets them back first, so that what a partial list does not cover
+    // is carried along, as in dav1d_hip_recon_list_run_tiled)
+    if (const int ru = dav1d_hip_picture_untile(c, dst)) return ru;
     const bool direct = recon_list_twin_direct(c, l, dst, refs, n_refs);
     dst->twin_ok = 0;
     if (direct) {
@@ -2265,6 +2288,7 @@ static int recon_list_run_timed_impl(Dav1dHipContext *c, const Dav1dHipReconList
 int dav1d_hip_recon_list_run_timed(Dav1dHipContext *c, const Dav1dHipReconList *l, const Dav1dHipPicture *dst,
                                    const Dav1dHipPicture *refs, int n_refs, int16_t *prep, uint8_t *mask, void *coef,
                                    float *ms, size_t *counts) {
+    if (!raster_dst_ok(dst)) return -EINVAL;
     return recon_list_run_timed_impl(c, l, dst, refs, n_refs, prep, mask, coef, ms, counts, nullptr);
 }
 // the launches of dav1d_hip_recon_list_run_tiled the same way (-ENOTSUP when the list cannot run with its picture in the twin only)
@@ -2611,7 +2635,7 @@ int dav1d_hip_intra_flow_create(Dav1dHipContext *c, Dav1dHipIntraFlow **out, con
 
 // enqueues: counters to zero, then the launch
 int dav1d_hip_intra_flow_run(Dav1dHipContext *c, const Dav1dHipIntraFlow *l, const Dav1dHipPicture *dst, void *coef, uint8_t *aux) {
-    if (!c || !l || !dst || (l->needs_aux && !aux)) return -EINVAL;
+    if (!c || !l || !raster_dst_ok(dst) || (l->needs_aux && !aux)) return -EINVAL;
     if (!l->n_units) return 0;
     if (hipMemsetAsync(l->ctr, 0, l->ctr_bytes, c->stream) != hipSuccess) return -EIO;
     const DevPlanes dp = dev_planes(dst);
@@ -2706,7 +2730,7 @@ int dav1d_hip_intra_sb_create(Dav1dHipContext *c, Dav1dHipIntraSb **out, const D
 // enqueues the launches on the context's stream: one per level, or (option intra_sb_flow, L2 hand-off form, more than one level) ONE
 // for all of them with the superblocks waiting for their neighbours' flags
 int dav1d_hip_intra_sb_run(Dav1dHipContext *c, const Dav1dHipIntraSb *l, const Dav1dHipPicture *dst, void *coef, uint8_t *aux) {
-    if (!c || !l || !dst || (l->needs_aux && !aux)) return -EINVAL;
+    if (!c || !l || !raster_dst_ok(dst) || (l->needs_aux && !aux)) return -EINVAL;
     const DevPlanes dp = dev_planes(dst);
     int rc = 0;
     const int lds = c->intra_sb_lds && !l->has_copies;          // (the LDS-resident form does not copy)
@@ -2753,7 +2777,7 @@ int dav1d_hip_intra_list_run_all(Dav1dHipContext *c, const Dav1dHipIntraList *l,
 // prep / mask: the scratch arena the PRED_TMP predictions of the batch go to and the blends read, and the mask arena
 int dav1d_hip_intra_list_run_batch_blend(Dav1dHipContext *c, const Dav1dHipIntraList *l, size_t batch, const Dav1dHipPicture *dst, void *coef,
                                          uint8_t *aux, int16_t *prep, uint8_t *mask) {
-    if (!c || !l || !dst || batch + 1 >= l->pair_start.size() || (l->needs_aux && !aux)) return -EINVAL;
+    if (!c || !l || !raster_dst_ok(dst) || batch + 1 >= l->pair_start.size() || (l->needs_aux && !aux)) return -EINVAL;
     const size_t n_blend = l->blend_start[batch + 1] - l->blend_start[batch];
     if (n_blend && (!prep || !mask)) return -EINVAL;
     const DevPlanes dp = dev_planes(dst);

@@ -224,7 +224,7 @@ namespace {
 // UNTILE: the other way (twin -> raster rows, for the rows [ty0 * 8, ...) the grid covers), same mapping
 template <typename pixel, bool UNTILE>
 __global__ __launch_bounds__(64) void retile_kernel(const pixel *__restrict__ src, pixel *__restrict__ twin, const int stride, const int h,
-                                                    const int n_xg, const int ty0)
+                                                    const int n_xg, const int ty0, const int y0, const int y1)
 {
     typedef typename std::conditional<sizeof(pixel) == 2, uint4, uint2>::type piece_t;
     constexpr int ROWS = 8;                   // tile rows (of 8 picture rows) per wave: 8 KB (4 KB) in flight per wave
@@ -236,7 +236,8 @@ __global__ __launch_bounds__(64) void retile_kernel(const pixel *__restrict__ sr
     const int n_ty = (h + 7) >> 3;
     piece_t v[ROWS];
     if (UNTILE) {
-        // `src` = the twin, `twin` = the raster plane; rows at or below h are not the picture's (a caller-wrapped plane need not have them)
+        // `src` = the twin, `twin` = the raster plane; rows at or below h are not the picture's (a caller-wrapped plane need not have them),
+        // rows outside [y0, y1) are not this call's (a band of dav1d_hip_host_picture_fetch: the raster rows of the other bands stay as they are)
 #pragma unroll
         for (int k = 0; k < ROWS; k++) {
             const int ty = dv::imin(ty0 + tyg * ROWS + k, n_ty - 1);
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(64) void retile_kernel(const pixel *__restrict__ sr
 #pragma unroll
         for (int k = 0; k < ROWS; k++) {
             const int y = (ty0 + tyg * ROWS + k) * 8 + r;
-            if (y < h) *reinterpret_cast<piece_t *>(twin + (size_t) y * stride + x) = v[k];
+            if (y >= y0 && y < y1) *reinterpret_cast<piece_t *>(twin + (size_t) y * stride + x) = v[k];
         }
         return;
     }
@@ -272,16 +273,16 @@ extern "C" int dav1d_hip_launch_retile(const DevPlanes *src, void *const twin[3]
         const dim3 grid((unsigned) n_xg * (unsigned) n_ty), wave(64);
         if (bpc == 8)
             hipLaunchKernelGGL((retile_kernel<uint8_t, false>), grid, wave, 0, (hipStream_t) stream, (const uint8_t *) src->data[pl], (uint8_t *) twin[pl],
-                               src->stride[pl], src->h[pl], n_xg, 0);
+                               src->stride[pl], src->h[pl], n_xg, 0, 0, src->h[pl]);
         else
             hipLaunchKernelGGL((retile_kernel<uint16_t, false>), grid, wave, 0, (hipStream_t) stream, (const uint16_t *) src->data[pl], (uint16_t *) twin[pl],
-                               src->stride[pl], src->h[pl], n_xg, 0);
+                               src->stride[pl], src->h[pl], n_xg, 0, 0, src->h[pl]);
     }
     return hip_rc(hipGetLastError());
 }
 
-// Twin -> raster planes (`dst`: the raster planes with their strides and heights), rows [row0[pl], row1[pl]) of each plane widened to
-// whole tile rows; plane_mask: bit pl = untile plane pl.  What a picture that lives in its twin only (DAV1D_HIP_TWIN_ONLY) goes
+// Twin -> raster planes (`dst`: the raster planes with their strides and heights), rows [row0[pl], row1[pl]) of each plane and no others
+// (the waves read whole tile rows and keep the rows asked for); plane_mask: bit pl = untile plane pl.  What a picture that lives in its twin only (DAV1D_HIP_TWIN_ONLY) goes
 // through before anything that reads raster planes — the fetch to the host first of all (src/picture.c:46-63's layout at the output only).
 extern "C" int dav1d_hip_launch_untile(const DevPlanes *dst, void *const twin[3], int bpc, const int row0[3], const int row1[3], int plane_mask, void *stream) {
     for (int pl = 0; pl < 3; pl++) {
@@ -295,10 +296,10 @@ extern "C" int dav1d_hip_launch_untile(const DevPlanes *dst, void *const twin[3]
         const dim3 grid((unsigned) n_xg * (unsigned) n_tyg), wave(64);
         if (bpc == 8)
             hipLaunchKernelGGL((retile_kernel<uint8_t, true>), grid, wave, 0, (hipStream_t) stream, (const uint8_t *) twin[pl], (uint8_t *) dst->data[pl],
-                               dst->stride[pl], h, n_xg, ty0);
+                               dst->stride[pl], h, n_xg, ty0, r0, r1);
         else
             hipLaunchKernelGGL((retile_kernel<uint16_t, true>), grid, wave, 0, (hipStream_t) stream, (const uint16_t *) twin[pl], (uint16_t *) dst->data[pl],
-                               dst->stride[pl], h, n_xg, ty0);
+                               dst->stride[pl], h, n_xg, ty0, r0, r1);
     }
     return hip_rc(hipGetLastError());
 }

@@ -105,7 +105,7 @@ typedef struct Dev {
     pthread_t thread[3];
     int have_threads;
     void *targ[3][3];
-    atomic_int n_frames, n_peer_copies, n_band_copies;
+    atomic_int n_frames, n_peer_copies, n_band_copies, n_twin_only;
 } Dev;
 
 /* a frame ends badly because a frame it predicts from did: dav1d's error (DAV1D_ERR(EINVAL), as check_tile makes it), not the backend's */
@@ -552,6 +552,7 @@ static int stage_end(Dav1dHipGlue *const g, Dav1dFrameContext *const f, Dav1dHip
     if (!rc && g->o.row_progress) rc = hip->frame_set_progress_callback(s->frame, rows_final, f);
     if (!rc) rc = hip->frame_end(s->frame, g->o.pack ? NULL : b->coef, b->prep, b->mask, filtered, NULL);
     atomic_fetch_add(&g->dev[s->dev].n_frames, 1);
+    if (!rc && filtered->twin_ok == DAV1D_HIP_TWIN_ONLY) atomic_fetch_add(&g->dev[s->dev].n_twin_only, 1);
     if (g->o.frame_end_seconds) g->o.frame_end_seconds(g->o.cookie, f, now_s() - t0);
     stat_add(g, DAV1D_HIP_GLUE_STAT_FRAME_END, t0);
     hip->lister_destroy(s->lister);
@@ -717,6 +718,7 @@ int dav1d_hip_glue_device_stats(const Dav1dHipGlue *const g, const int d, int *c
     return 0;
 }
 int dav1d_hip_glue_band_copies(const Dav1dHipGlue *const g, const int d) { return g && d >= 0 && d < g->n_dev ? atomic_load(&g->dev[d].n_band_copies) : 0; }
+int dav1d_hip_glue_twin_only_frames(const Dav1dHipGlue *const g, const int d) { return g && d >= 0 && d < g->n_dev ? atomic_load(&g->dev[d].n_twin_only) : 0; }
 int dav1d_hip_glue_live_objects(const Dav1dHipGlue *const g, long long out[4]) { return g && g->hip.live_objects ? g->hip.live_objects(out) : DAV1D_ERR(EINVAL); }
 
 /* ------------------------------------------------------------------------------------------------ life cycle */

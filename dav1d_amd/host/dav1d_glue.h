@@ -110,6 +110,9 @@ int dav1d_hip_glue_devices(const Dav1dHipGlue *g);
 int dav1d_hip_glue_device_stats(const Dav1dHipGlue *g, int d, int *frames_ended, int *peer_copies);
 /* bands of other devices' pictures that crossed to device d while their frames were still ending, or as the remainder behind such bands (option row_progress) */
 int dav1d_hip_glue_band_copies(const Dav1dHipGlue *g, int d);
+/* frames that ended on device d with their picture in its tiled twin only (DAV1D_HIP_TWIN_ONLY: context option ref_twin = 3, a frame that is
+ * reconstruction and nothing else): what the output calls below and later frames then read */
+int dav1d_hip_glue_twin_only_frames(const Dav1dHipGlue *g, int d);
 /* objects of libdav1d_hip alive (dav1d_hip_live_objects): contexts, frames, listers, host pictures */
 int dav1d_hip_glue_live_objects(const Dav1dHipGlue *g, long long out[4]);
 #endif

@@ -136,7 +136,11 @@ typedef struct Dav1dHipPicture {
      * tiles — an 8x8 block is one 128-byte line — and nothing else).  Such a picture may be handed to motion compensation as a
      * reference, to dav1d_hip_host_picture_fetch / dav1d_hip_plane_download (they un-tile the rows they copy: raster rows by the
      * address rules of the reference's src/picture.c:46-63 exist at the output only), to dav1d_hip_recon_list_run_tiled again and to
-     * dav1d_hip_picture_untile, which gives the raster planes back (twin_ok = 1) for everything else. */
+     * dav1d_hip_picture_untile, which gives the raster planes back (twin_ok = 1) for everything else.  As a SOURCE of any other
+     * entry point (`src`, `lpf`, `refs`) it is un-tiled first, in the record handed over (twin_ok = 1 there); as the `dst` of an entry
+     * point that writes raster planes (a `const Dav1dHipPicture *dst`) it is refused with -EINVAL before anything is enqueued.  The
+     * exceptions are the measurement aids dav1d_hip_itx_list_run_timed, dav1d_hip_mc_list_run_timed and dav1d_hip_inter_list_run_timed:
+     * they write the raster planes of a picture in any state and leave twin_ok alone (what they leave there is not the picture). */
     void *twin[3];
     void *twin_alloc;
     int twin_ok;

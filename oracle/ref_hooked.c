@@ -70,7 +70,10 @@ typedef struct HookedParams {
                                   references (decode_b's lowest_pixel bookkeeping) and start while this frame's filters still run */
     int apply_grain;           /* stream mode: film grain on the output pictures — mode 0: Dav1dSettings.apply_grain (dav1d_apply_grain on the
                                   host); mode 1: apply_grain = 0 and the "application" applies it on the device (dav1d_hip_fg_apply on the picture
-                                  dav1d returns, frame_hdr->film_grain.data), as GPU video outputs do */
+                                  dav1d returns, frame_hdr->film_grain.data), as GPU video outputs do.
+                                  chain mode: every frame header carries a grain set with luma scaling points and none for chroma (the chroma
+                                  planes of the output are copies), and the pictures kept are the ones with grain — mode 0: dav1d_apply_grain
+                                  (src/lib.c:485-524) on the picture dav1d hands out, mode 1: dav1d_hip_glue_output_with_grain */
     int filters_off;           /* in-loop filters the "application" switches off, both modes: Dav1dSettings.inloop_filters = ALL & ~filters_off
                                   (bit 0 deblock, 1 CDEF, 2 restoration; include/dav1d/dav1d.h:61-69) */
     int n_devices;             /* mode 1: Dav1dHipGlueOptions.n_devices — frames end on devices device .. device + n_devices - 1 in turn */
@@ -692,15 +695,68 @@ static void fill_frame(Dav1dFrameHeader *const fh, const HookedParams *const p, 
     for (int i = 0; i < 3; i++) fh->restoration.type[i] = p->lr_type[i];
     fh->restoration.unit_size[0] = p->lr_unit_size[0]; fh->restoration.unit_size[1] = p->lr_unit_size[1];
     for (int i = 0; i < 7; i++) fh->gmv[i] = dav1d_default_wm_params;
+    if (p->apply_grain && !p->stream) {
+        /* luma scaling points only: dav1d_apply_grain copies both chroma planes from the source picture (src/fg_apply_tmpl.c:127-163) */
+        Dav1dFilmGrainData *const fg = &fh->film_grain.data;
+        fh->film_grain.present = 1; fh->film_grain.update = 1;
+        fg->seed = (unsigned) (1234 + 977 * k) & 0xffff;
+        fg->num_y_points = 3;
+        fg->y_points[0][0] = 0;   fg->y_points[0][1] = 48;
+        fg->y_points[1][0] = 128; fg->y_points[1][1] = 96 + 8 * (k & 3);
+        fg->y_points[2][0] = 255; fg->y_points[2][1] = 32;
+        fg->scaling_shift = 10; fg->ar_coeff_lag = 2; fg->ar_coeff_shift = 7;
+        for (int i = 0; i < 12; i++) fg->ar_coeffs_y[i] = (int8_t) ((i * 7 + k) % 17 - 8);
+        fg->overlap_flag = 1;
+    }
 }
 
 /* ------------------------------------------------------------------------------------------------ outputs */
 static uint64_t hash_bytes(uint64_t x, const uint8_t *p, size_t n);
+static int pic_has_grain(const Dav1dPicture *pic);
+/* chain mode with HookedParams.apply_grain: frame k's picture with its film grain, as tight planes (or their digests) */
+static void keep_picture_with_grain(Hooked *const h, const Dav1dPicture *const pic, const int k) {
+    const int bps = pic->p.bpc > 8 ? 2 : 1, n_pl = pic->p.layout == DAV1D_PIXEL_LAYOUT_I400 ? 1 : 3;
+    const int ss_hor = pic->p.layout != DAV1D_PIXEL_LAYOUT_I444, ss_ver = pic->p.layout == DAV1D_PIXEL_LAYOUT_I420;
+    uint8_t *planes[3] = { NULL, NULL, NULL };
+    int rc = 0;
+    for (int pl = 0; pl < n_pl; pl++) {
+        const int w = pl ? (pic->p.w + ss_hor) >> ss_hor : pic->p.w, hh = pl ? (pic->p.h + ss_ver) >> ss_ver : pic->p.h;
+        planes[pl] = malloc((size_t) w * hh * bps);
+        if (!planes[pl]) rc = -ENOMEM;
+    }
+    if (!rc && h->p.mode == 1) rc = dav1d_hip_glue_output_with_grain(h->glue, pic, planes);
+    else if (!rc) {
+        Dav1dPicture grained;
+        memset(&grained, 0, sizeof(grained));
+        rc = dav1d_apply_grain(h->c, &grained, pic);
+        for (int pl = 0; pl < n_pl && !rc; pl++) {
+            const int w = pl ? (pic->p.w + ss_hor) >> ss_hor : pic->p.w, hh = pl ? (pic->p.h + ss_ver) >> ss_ver : pic->p.h;
+            for (int y = 0; y < hh; y++) memcpy(planes[pl] + (size_t) y * w * bps, (const uint8_t *) grained.data[pl] + (ptrdiff_t) y * grained.stride[!!pl], (size_t) w * bps);
+        }
+        if (grained.data[0]) dav1d_picture_unref(&grained);
+    }
+    for (int pl = 0; pl < n_pl; pl++) {
+        const int w = pl ? (pic->p.w + ss_hor) >> ss_hor : pic->p.w, hh = pl ? (pic->p.h + ss_ver) >> ss_ver : pic->p.h;
+        if (rc) { free(planes[pl]); continue; }
+        if (h->p.keep_output == 2) {
+            uint64_t x = 0xDA71Dull + (uint64_t) pl;
+            for (int y = 0; y < hh; y++) x = hash_bytes(x, planes[pl] + (size_t) y * w * bps, (size_t) w * bps);
+            h->out_hash[k * 3 + pl] = x;
+            free(planes[pl]);
+        } else {
+            free(h->out_plane[k * 3 + pl]);
+            h->out_plane[k * 3 + pl] = planes[pl];
+        }
+    }
+    if (rc) h->failed = 1;
+}
+
 static void keep_picture(Hooked *const h, const Dav1dPicture *const pic) {
     const int k = pic->frame_hdr->frame_offset;
     if (k < 0 || k >= h->p.n_frames) return;
     h->n_out++;
     h->out_t[k] = now_s();                /* when dav1d_get_picture / dav1d_submit_frame handed frame k out (either mode) */
+    if (h->p.keep_output && h->p.apply_grain && pic_has_grain(pic)) { keep_picture_with_grain(h, pic, k); return; }
     if (h->p.keep_output == 2) {          /* digests of the visible rows only (long chains of large pictures) */
         const int bps2 = pic->p.bpc > 8 ? 2 : 1;
         const int ssh = pic->p.layout != DAV1D_PIXEL_LAYOUT_I444, ssv = pic->p.layout == DAV1D_PIXEL_LAYOUT_I420;
@@ -881,6 +937,7 @@ int dav1d_hooked_device_stats(void *const handle, const int d, int out[2]) {
     return dav1d_hip_glue_devices(((Hooked *) handle)->glue);
 }
 int dav1d_hooked_band_copies(void *const handle, const int d) { return handle && ((Hooked *) handle)->glue ? dav1d_hip_glue_band_copies(((Hooked *) handle)->glue, d) : 0; }
+int dav1d_hooked_twin_only_frames(void *const handle, const int d) { return handle && ((Hooked *) handle)->glue ? dav1d_hip_glue_twin_only_frames(((Hooked *) handle)->glue, d) : 0; }
 int dav1d_hooked_row_publications(void *const handle) { return handle ? dav1d_hip_glue_row_publications(((Hooked *) handle)->glue) : 0; }
 int dav1d_hooked_n_fc(void *const handle) { return handle ? (int) ((Hooked *) handle)->n_fc : 0; }
 

@@ -42,6 +42,7 @@ def lib():
     l.dav1d_hooked_device_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int * 2)]
     if hasattr(l, "dav1d_hooked_band_copies"):
         l.dav1d_hooked_band_copies.argtypes = [C.c_void_p, C.c_int]
+    l.dav1d_hooked_twin_only_frames.argtypes = [C.c_void_p, C.c_int]
     l.dav1d_hooked_tail_seconds.restype = C.c_double
     l.dav1d_hooked_tail_seconds.argtypes = [C.c_void_p, C.c_int]
     l.dav1d_hooked_output_tail_seconds.restype = C.c_double
@@ -57,7 +58,7 @@ FILTERS = dict(lf=(20, 28, 16, 24, 0), cdef=(5, 2, [17, 33, 0, 63], [5, 0, 20, 4
 
 
 def params(w, h, bpc, n_frames, mode, layout=1, sb128=True, tiles=(2, 1), threads=4, frame_delay=3, filters=FILTERS, seed=5, free_listing=1,
-           keep_output=True, synth=None, pack=True, row_progress=0, n_devices=0):
+           keep_output=True, synth=None, pack=True, row_progress=0, n_devices=0, apply_grain=0):
     p = HookedParams()
     p.w, p.h, p.layout, p.bpc, p.sb128 = w, h, layout, bpc, int(sb128)
     sb = 128 if sb128 else 64
@@ -83,6 +84,7 @@ def params(w, h, bpc, n_frames, mode, layout=1, sb128=True, tiles=(2, 1), thread
     p.mode, p.free_listing, p.device, p.keep_output = mode, free_listing, 0, int(keep_output)
     p.row_progress = int(row_progress)
     p.n_devices = int(n_devices)
+    p.apply_grain = int(apply_grain)          # chain mode: luma-only film grain on every output picture (oracle/ref_hooked.c)
     p.pack = int(bool(pack) and mode == 1 and os.environ.get("DAV1D_HOOKED_PACK", "1") != "0")
     p.synth = synth if synth is not None else lu.default_synth(seed, n_refs=3, far_mv_pct=2)
     return p
@@ -121,6 +123,7 @@ def run(p, hip_lib_path, store=None, inject=0):
             for d in range(max(1, l.dav1d_hooked_device_stats(h, 0, C.byref(ds)))):
                 l.dav1d_hooked_device_stats(h, d, C.byref(ds))
                 run.last_device_stats.append((int(ds[0]), int(ds[1])))
+            run.last_twin_only_frames = sum(int(l.dav1d_hooked_twin_only_frames(h, d)) for d in range(len(run.last_device_stats)))
             run.last_band_copies = [int(l.dav1d_hooked_band_copies(h, d)) for d in range(len(run.last_device_stats))] if hasattr(l, "dav1d_hooked_band_copies") else []
         st = (C.c_double * 16)()
         l.dav1d_hooked_stats(h, st)

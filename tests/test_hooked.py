@@ -95,3 +95,31 @@ def test_rows_cross_to_the_other_device_while_their_frame_is_still_ending(ctx):
     assert len(st) == 2 and st[0][1] + st[1][1] >= n_frames - 1, st
     assert hk.run.last_row_publications > n_frames, hk.run.last_row_publications       # rows came band by band
     assert sum(bands) > 0, (bands, st)            # ... and crossed that way at least once
+
+
+def test_grain_on_the_output_of_frames_that_live_in_their_twins(ctx, monkeypatch):
+    """DAV1D_HIP_REF_TWIN=3: an inter frame that is reconstruction and nothing else (no intra blocks, no warped or blended predictions, no
+    in-loop filters) ends with its picture in the tiled twin ONLY, and the binding hands that picture to dav1d_hip_fg_apply as it is
+    (dav1d_hip_glue_output_with_grain).  The grain sets have luma scaling points and none for chroma, so both chroma planes of the output are
+    copies of the source's — taken from the twin, not from the stale raster planes.  Every output picture equals dav1d's own
+    (dav1d_apply_grain on the picture its C pass 2 made).
+    (The binding fetches every picture to the host before it is handed out, and that fetch stages all visible rows in the raster planes:
+    a reader that skips the un-tile finds valid rows there.  What this case holds is that such frames occur, pass through the entry
+    points as twin-only pictures without a refusal, and come out as dav1d's; the stale-plane reads themselves are caught in
+    tests/test_picture_states.py, where nothing stages the raster planes.)"""
+    import lister_util as lu
+    monkeypatch.setenv("DAV1D_HIP_REF_TWIN", "3")
+    w, h, bpc = 320, 200, 10
+    n_frames = 5 if ctx.backend == "emu" else 8
+    sp = lu.default_synth(11, n_refs=3, far_mv_pct=2, intra_pct=0, masked_compound=0, global_pct=0, interintra_pct=0, obmc_pct=0, warp_pct=0)
+    kw = dict(tiles=(2, 1), filters=None, synth=sp, apply_grain=1)
+    _, _, want = hk.run(hk.params(w, h, bpc, n_frames, mode=0, **kw), hip_lib_path(ctx))
+    plain = hk.run(hk.params(w, h, bpc, n_frames, mode=0, **dict(kw, apply_grain=0)), hip_lib_path(ctx))[2]
+    _, _, got = hk.run(hk.params(w, h, bpc, n_frames, mode=1, **kw), hip_lib_path(ctx))
+    assert hk.run.last_twin_only_frames >= 1, "no frame of the chain ended DAV1D_HIP_TWIN_ONLY"
+    for k in range(n_frames):
+        # the grain is there, on luma only: the chroma planes are the ungrained picture's
+        assert not np.array_equal(want[k][0], plain[k][0]) and np.array_equal(want[k][1], plain[k][1]) and np.array_equal(want[k][2], plain[k][2])
+        for pl in range(3):
+            bad = np.argwhere(want[k][pl] != got[k][pl])
+            assert not len(bad), "frame %d plane %d differs at %s (%d pixels)" % (k, pl, bad[0], len(bad))

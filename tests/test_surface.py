@@ -15,63 +15,13 @@ import synth_frames as synth
 import test_frame
 import test_filmgrain
 from dav1d_amd import api
+from util import STATES, forget_raster, make_source          # the three picture states: shared with tests/test_picture_states.py
 
 EINVAL, ENOTSUP = 22, 95
 SENTINEL = 0xA5
 LAYOUTS = [api.LAYOUT_I400, api.LAYOUT_I420, api.LAYOUT_I422, api.LAYOUT_I444]
 SIZES = [(190, 102), (64, 64), (333, 77)]
-STATES = ["raster", "retiled", "twin-only"]
 MATRICES = {1: (0.2126, 0.0722), 5: (0.299, 0.114), 6: (0.299, 0.114), 9: (0.2627, 0.0593)}
-
-
-# ------------------------------------------------------------------------------------------------ sources
-
-def random_planes(rng, pic, extremes=False):
-    """padded planes for pic.upload; `extremes`: every combination of 0 / mid / max in Y, U, V somewhere in the visible area"""
-    bpc = pic.bpc
-    out = []
-    for pl in range(pic.n_planes):
-        a = rng.integers(0, 1 << bpc, size=pic.padded_shape(pl)).astype(pic.dtype)
-        out.append(a)
-    if extremes:
-        vals = [0, 1 << (bpc - 1), (1 << bpc) - 1]
-        ss_h = 1 if pic.layout in (api.LAYOUT_I420, api.LAYOUT_I422) else 0
-        ss_v = 1 if pic.layout == api.LAYOUT_I420 else 0
-        k = 0
-        for y in vals:
-            for u in vals:
-                for v in vals:
-                    # a 2x2 luma patch over one chroma sample (one luma sample at 4:4:4), along the first rows
-                    cx, cy = k % 24, 2 * (k // 24)
-                    out[0][(cy << ss_v):((cy + 1) << ss_v), (cx << ss_h):((cx + 1) << ss_h)] = y
-                    if pic.n_planes == 3:
-                        out[1][cy, cx], out[2][cy, cx] = u, v
-                    k += 1
-    return out
-
-
-def make_source(ctx, rng, w, h, layout, bpc, state, extremes=False):
-    """a device picture in one of the three states a decoded picture can be in, and its visible planes"""
-    pic = ctx.picture(w, h, layout, bpc)
-    planes = random_planes(rng, pic, extremes)
-    for pl in range(pic.n_planes):
-        pic.upload(pl, planes[pl])
-    if state == "raster":
-        assert pic.pic.twin_ok == 0
-    else:
-        pic.retile()
-        assert pic.pic.twin_ok == 1
-    if state == "twin-only":
-        forget_raster(ctx, pic)
-    vis = [planes[pl][:pic.pic.p[pl].h, :pic.pic.p[pl].w] for pl in range(pic.n_planes)]
-    return pic, vis
-
-
-def forget_raster(ctx, pic):
-    """the raster planes become 0x5A everywhere (the twin has an allocation of its own): any read of them shows"""
-    assert pic.pic.twin_alloc and pic.pic.twin_alloc != pic.pic.alloc
-    assert ctx.lib.dav1d_hip_memset(ctx.h, pic.pic.alloc, 0x5A, pic.pic.alloc_size) == 0
-    pic.pic.twin_ok = api.TWIN_ONLY
 
 
 # ------------------------------------------------------------------------------------------------ expectations (numpy)

@@ -358,3 +358,81 @@ def replay_lib():
     lib.dav1d_replay_cdef.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     lib.dav1d_replay_lr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     return lib
+
+
+# ------------------------------------------------------------- picture states
+
+# A Dav1dHipPicture is in one of three states (include/dav1d_hip.h, twin_ok): the raster planes are the picture (0), raster planes and
+# tiled twin agree (1), the picture lives in its twin and the raster planes are stale (DAV1D_HIP_TWIN_ONLY).
+STATES = ["raster", "retiled", "twin-only"]
+
+
+def random_planes(rng, pic, extremes=False):
+    """padded planes for pic.upload; `extremes`: every combination of 0 / mid / max in Y, U, V somewhere in the visible area"""
+    from dav1d_amd import api
+    bpc = pic.bpc
+    out = []
+    for pl in range(pic.n_planes):
+        a = rng.integers(0, 1 << bpc, size=pic.padded_shape(pl)).astype(pic.dtype)
+        out.append(a)
+    if extremes:
+        vals = [0, 1 << (bpc - 1), (1 << bpc) - 1]
+        ss_h = 1 if pic.layout in (api.LAYOUT_I420, api.LAYOUT_I422) else 0
+        ss_v = 1 if pic.layout == api.LAYOUT_I420 else 0
+        k = 0
+        for y in vals:
+            for u in vals:
+                for v in vals:
+                    # a 2x2 luma patch over one chroma sample (one luma sample at 4:4:4), along the first rows
+                    cx, cy = k % 24, 2 * (k // 24)
+                    out[0][(cy << ss_v):((cy + 1) << ss_v), (cx << ss_h):((cx + 1) << ss_h)] = y
+                    if pic.n_planes == 3:
+                        out[1][cy, cx], out[2][cy, cx] = u, v
+                    k += 1
+    return out
+
+
+def forget_raster(ctx, pic):
+    """the raster planes become 0x5A everywhere (the twin has an allocation of its own): any read of them shows"""
+    from dav1d_amd import api
+    assert pic.pic.twin_alloc and pic.pic.twin_alloc != pic.pic.alloc
+    assert ctx.lib.dav1d_hip_memset(ctx.h, pic.pic.alloc, 0x5A, pic.pic.alloc_size) == 0
+    pic.pic.twin_ok = api.TWIN_ONLY
+
+
+def put_in_state(ctx, pic, state):
+    """an uploaded picture (or one a guarded reader has un-tiled since) into `state`, its pixels unchanged"""
+    from dav1d_amd import api
+    if state == "raster":
+        assert pic.pic.twin_ok == 0
+        return
+    if pic.pic.twin_ok == 0:
+        pic.retile()
+    if state == "twin-only" and pic.pic.twin_ok == 1:
+        forget_raster(ctx, pic)
+    assert pic.pic.twin_ok == {"retiled": 1, "twin-only": api.TWIN_ONLY}[state]
+
+
+def make_source(ctx, rng, w, h, layout, bpc, state, extremes=False):
+    """a device picture in one of the three states a decoded picture can be in, and its visible planes"""
+    pic = ctx.picture(w, h, layout, bpc)
+    planes = random_planes(rng, pic, extremes)
+    for pl in range(pic.n_planes):
+        pic.upload(pl, planes[pl])
+    put_in_state(ctx, pic, state)
+    vis = [planes[pl][:pic.pic.p[pl].h, :pic.pic.p[pl].w] for pl in range(pic.n_planes)]
+    return pic, vis
+
+
+def twin_bytes(ctx, pic):
+    """every byte of the twin's storage (dav1d_hip_picture_twin_alloc: per plane stride x padded rows, each rounded up to 256 bytes)"""
+    total = 0
+    for pl in range(3):
+        if pic.pic.p[pl].data:
+            ss_ver = 1 if pl and pic.pic.layout == 1 else 0
+            total += pic.pic.p[pl].stride * (((pic.pic.p[0].h + 127) & ~127) >> ss_ver)
+            total = (total + 255) & ~255
+    out = np.zeros(total, np.uint8)
+    ctx.sync()
+    assert ctx.lib.dav1d_hip_download(ctx.h, out.ctypes.data, pic.pic.twin_alloc, total) == 0
+    return out
