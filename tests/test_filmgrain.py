@@ -115,3 +115,65 @@ def test_film_grain_matches_reference(ctx, bpc, variant):
             assert not len(bad), "plane %d differs at %s: got %d want %d (%d px, split=%s)" % (
                 pl, bad[0], got[tuple(bad[0])], want[pl][tuple(bad[0])], len(bad), split)
     src.free(); dst.free()
+
+
+# 4:2:2 (chroma subsampled across only), 4:0:0 (one plane, one-plane launch grid) and a picture whose last block row and column are
+# cut on odd coordinates: (layout, emulator size, device size)
+LAYOUT_CASES = {
+    "i422": (api.LAYOUT_I422, (160, 96), (736, 416)),
+    "i400": (api.LAYOUT_I400, (160, 96), (736, 416)),
+    "i420-odd-odd": (api.LAYOUT_I420, (157, 83), (733, 403)),
+    "i422-odd-odd": (api.LAYOUT_I422, (157, 83), (733, 403)),
+}
+
+
+@pytest.mark.parametrize("case", list(LAYOUT_CASES))
+@pytest.mark.parametrize("bpc", [8, 10, 12])
+def test_film_grain_layouts_and_odd_sizes(ctx, bpc, case):
+    """The comparisons of test_film_grain_matches_reference on the layouts and sizes it leaves out: 4:2:2, 4:0:0, and both dimensions
+    odd with a height that is no multiple of the 32-row block."""
+    layout, emu_size, hip_size = LAYOUT_CASES[case]
+    w, h = emu_size if ctx.backend == "emu" else hip_size
+    if "odd" in case:
+        assert w & 1 and h & 1 and h % 32
+    lib = fg_driver()
+    rng = np.random.default_rng(3300 + 10 * bpc + len(case))
+    data = random_fg(rng, bpc, 0)
+    n_planes = 1 if layout == api.LAYOUT_I400 else 3
+    if n_planes == 1:       # a monochrome stream carries no chroma scaling points (the frame header parser leaves them 0)
+        data.num_uv_points[0] = data.num_uv_points[1] = 0
+    want_lut = np.zeros((3, 74, 82), np.int16)
+    lib.generate_grain(bpc, C.byref(data), layout, want_lut.ctypes.data)
+    got_lut = ctx.fg_generate_grain(data, bpc, layout)
+    assert np.array_equal(got_lut[0], want_lut[0]), "luma grain template"
+    if n_planes == 3:
+        assert np.array_equal(got_lut, want_lut), "chroma grain templates"
+    src = ctx.picture(w, h, layout, bpc)
+    dst = ctx.picture(w, h, layout, bpc)
+    planes = synth.make_planes(rng, w, h, bpc, smooth=True, layout=layout)
+    assert len(planes) == n_planes and all(planes[pl].shape == src.padded_shape(pl) for pl in range(n_planes))
+    out0 = [np.zeros_like(p.base)[:, :p.shape[1]] for p in planes]
+    for pl in range(n_planes):
+        src.upload(pl, planes[pl])
+    want = synth.copy_planes(out0)
+    inp = synth.copy_planes(planes)
+    outp = (C.c_void_p * 3)(*([p.ctypes.data for p in want] + [None] * (3 - n_planes)))
+    inpp = (C.c_void_p * 3)(*([p.ctypes.data for p in inp] + [None] * (3 - n_planes)))
+    lib.apply_grain(bpc, C.byref(data), w, h, layout, 0, outp, inpp, want[0].strides[0], want[-1].strides[0] if n_planes == 3 else 0)
+    ss_v, ss_h = (1 if layout == api.LAYOUT_I420 else 0), (1 if layout != api.LAYOUT_I444 else 0)
+    for split in (False, True):
+        for pl in range(n_planes):
+            dst.upload(pl, out0[pl])
+        if split:
+            g = ctx.fg_prepare(data, bpc, layout)
+            ctx.fg_apply_prepared(dst, src, g, 0)
+            ctx.fg_grain_destroy(g)
+        else:
+            ctx.fg_apply(dst, src, data, 0)
+        for pl in range(n_planes):
+            vh, vw = (h, w) if pl == 0 else ((h + ss_v) >> ss_v, (w + ss_h) >> ss_h)
+            got = dst.download(pl)[:vh, :vw]
+            bad = np.argwhere(got != want[pl][:vh, :vw])
+            assert not len(bad), "%s, plane %d differs at %s: got %d want %d (%d px, split=%s)" % (
+                case, pl, bad[0], got[tuple(bad[0])], want[pl][tuple(bad[0])], len(bad), split)
+    src.free(); dst.free()
