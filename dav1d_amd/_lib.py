@@ -85,7 +85,7 @@ SYMBOLS = [
     "dav1d_hip_lister_create", "dav1d_hip_lister_tile_sbrow", "dav1d_hip_lister_run", "dav1d_hip_lister_filter_run", "dav1d_hip_lister_run_frame", "dav1d_hip_lister_prep_elems", "dav1d_hip_lister_mask_bytes",
     "dav1d_hip_lister_steps", "dav1d_hip_lister_const_masks", "dav1d_hip_lister_destroy",
     "dav1d_hip_lister_mask_offset", "dav1d_hip_lister_tables", "dav1d_hip_lister_block_warp", "dav1d_hip_lister_filter_sbrow",
-    "dav1d_hip_surface_export",
+    "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain",
 ]
 
 
@@ -285,6 +285,7 @@ def load(path=None):
         "dav1d_hip_picture_copy_peer_rows": (i, [vp, P(Picture), vp, P(Picture), C.c_int, C.c_int]),
         "dav1d_hip_enable_peer_access": (i, [vp, vp]),
         "dav1d_hip_surface_export": (i, [vp, P(Surface), P(Picture), i, i]),
+        "dav1d_hip_surface_export_grain": (i, [vp, P(Surface), P(Picture), vp, i, i, i]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

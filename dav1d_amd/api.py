@@ -117,9 +117,14 @@ class DevicePicture:
                                                    out.strides[0], 1), "plane_download")
         return out
 
-    def export(self, surface, row0=0, row1=1 << 30):
+    def export(self, surface, row0=0, row1=1 << 30, grain=None, is_id=0):
         """dav1d_hip_surface_export: luma rows [row0, row1) of this picture into a device surface of the caller, on the context's stream
-        (asynchronous; a picture that lives in its twin only is read through the twin and stays there)."""
+        (asynchronous; a picture that lives in its twin only is read through the twin and stays there).  `grain` (a handle of
+        Context.fg_prepare): film grain is applied in the same pass (dav1d_hip_surface_export_grain); the picture itself is not changed."""
+        if grain is not None:
+            _chk(self.ctx.lib.dav1d_hip_surface_export_grain(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), grain, is_id, row0, row1),
+                 "surface_export_grain")
+            return
         _chk(self.ctx.lib.dav1d_hip_surface_export(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), row0, row1), "surface_export")
 
     @classmethod
@@ -203,11 +208,12 @@ class Surface:
         self.bufs = None
 
 
-def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30):
+def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0):
     """Fills torch tensors on the picture's device through tensor.data_ptr(): `tensor` of shape (3, h, w) gets R, G, B planes; with
     `chroma` of shape (ceil(h / 2), 2 * ceil(w / 2)) given, `tensor` (h, w) gets luma and `chroma` the interleaved U, V of a 4:2:0
     picture (NV12 / P010 family).  The sample type follows the dtype (float32: F32; else `sample`, native by default).  The context should
-    have been opened on the stream the tensors are used on (api.Context(stream=torch.cuda.current_stream().cuda_stream))."""
+    have been opened on the stream the tensors are used on (api.Context(stream=torch.cuda.current_stream().cuda_stream)).  `grain` / `is_id`:
+    as in DevicePicture.export."""
     import torch
     ts = [tensor] if chroma is None else [tensor, chroma]
     for t in ts:
@@ -231,7 +237,7 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     s = Surface.wrap(pic.ctx, ptrs, strides, pic.w, pic.h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
     if s.dtype.itemsize != es or [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]:
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
-    pic.export(s, row0, row1)
+    pic.export(s, row0, row1, grain=grain, is_id=is_id)
     return s
 
 

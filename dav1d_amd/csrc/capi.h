@@ -389,6 +389,24 @@ extern "C" int dav1d_hip_launch_fg_apply(const DevPlanes *dst, const DevPlanes *
                                          int scaling_size, const Dav1dHipFilmGrainData *data, int bpc, int layout, int is_id, uint8_t *offs,
                                          void *stream);
 
+extern "C" int dav1d_hip_launch_fg_offsets(uint8_t *offs, unsigned seed, int nrows, int nblk, void *stream);
+
+// Grain templates + scaling tables of one frame (dav1d_hip_fg_prepare, capi.hip), and the per-block random offsets of the picture geometries the
+// fused export (surface_grain.hip) met: a table depends on the seed and the block counts only, is built on the context's stream the first time
+// its geometry is seen and lives until dav1d_hip_fg_grain_destroy, so a call that returns at once leaves nothing behind that could go away under
+// its kernels.  `offs` is the one part of a handle that changes after dav1d_hip_fg_prepare: a handle serves one context at a time.
+struct Dav1dHipGrain {
+    uint8_t *dev;
+    size_t lut_bytes, scaling_size;
+    int bpc, layout;
+    Dav1dHipFilmGrainData data;
+    std::vector<uint8_t> sc;       // host copy of the scaling tables: kept alive for the asynchronous upload
+    hipEvent_t ready;
+    hipStream_t side;
+    struct Offsets { uint8_t *dev; int nbx, nby; };
+    mutable std::vector<Offsets> offs;
+};
+
 extern "C" int dav1d_hip_launch_fg_gen_part(int16_t *luts, const Dav1dHipFilmGrainData *data, int bpc, int layout, int part, void *stream);
 extern "C" int dav1d_hip_launch_fg_apply_rows(const DevPlanes *dst, const DevPlanes *src, const int16_t *luts, const uint8_t *scaling,
                                               int scaling_size, const Dav1dHipFilmGrainData *data, int bpc, int layout, int is_id,

@@ -1824,16 +1824,6 @@ extern "C" int dav1d_hip_fg_generate_grain(Dav1dHipContext *c, const Dav1dHipFil
 // on the frame header only, so they are generated on a side stream as soon as the parameters are known — a lone wave per
 // template, ~0.23 ms of latency that then hides behind the reconstruction of the frame — and dav1d_hip_fg_apply_prepared
 // (the dav1d_apply_grain_row part) only waits for their event.
-struct Dav1dHipGrain {
-    uint8_t *dev;
-    size_t lut_bytes, scaling_size;
-    int bpc, layout;
-    Dav1dHipFilmGrainData data;
-    std::vector<uint8_t> sc;       // host copy of the scaling tables: kept alive for the asynchronous upload
-    hipEvent_t ready;
-    hipStream_t side;
-};
-
 static int fg_prepare_on(Dav1dHipContext *c, Dav1dHipGrain **out, const Dav1dHipFilmGrainData *data, int bpc, int layout, hipStream_t stream) {
     if (!c || !out || !data || (bpc != 8 && bpc != 10 && bpc != 12) || layout < 0 || layout > 3) return -EINVAL;
     *out = nullptr;
@@ -1868,6 +1858,7 @@ extern "C" void dav1d_hip_fg_grain_destroy(Dav1dHipContext *c, Dav1dHipGrain *g)
     hipStreamSynchronize(g->side);
     if (c) hipStreamSynchronize(c->stream);
     hipFree(g->dev);
+    for (const Dav1dHipGrain::Offsets &o : g->offs) hipFree(o.dev);       // (the fused export's tables: surface_grain.hip)
     hipEventDestroy(g->ready);
     delete g;
 }

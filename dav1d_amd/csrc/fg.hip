@@ -14,29 +14,13 @@
 // offsets are the k-th outputs of the per-row LFSR, recomputed by every wave (<= 241 steps).
 #include "common.h"
 #include "capi.h"
+#include "fg_common.h"
 #include <type_traits>
 #include "av1_tables.h"
 #include <string.h>
 
 namespace {
 
-enum { GW = 82, GH = 73, SGW = 44, SGH = 38 };
-
-__device__ __forceinline__ unsigned lfsr_step(const unsigned r) {
-    const unsigned bit = ((r >> 0) ^ (r >> 1) ^ (r >> 3) ^ (r >> 12)) & 1;
-    return (r >> 1) | (bit << 15);
-}
-__device__ __forceinline__ int round2(const int x, const int shift) { return (x + ((1 << shift) >> 1)) >> shift; }
-
-struct FgParams {                 // the scalar part of Dav1dFilmGrainData the kernels need
-    unsigned seed;
-    int num_y_points, chroma_scaling_from_luma, num_uv_points[2];
-    int scaling_shift, ar_coeff_lag, ar_coeff_shift, grain_scale_shift;
-    int uv_mult[2], uv_luma_mult[2], uv_offset[2];
-    int overlap_flag, clip_to_restricted_range;
-    int8_t ar_coeffs_y[24];
-    int8_t ar_coeffs_uv[2][28];
-};
 
 // The auto-regressive pass of one template as a wavefront: lane = row, row y trails row y-1 by LAG+1 columns, so everything a
 // sample needs is final when its turn comes (src/filmgrain_tmpl.c:72-91, 123-153).  LAG is a compile-time constant so that the
@@ -196,14 +180,6 @@ __global__ __launch_bounds__(64) void fg_gen_kernel(int16_t *luts, const FgParam
     }
 }
 
-// sample_lut, src/filmgrain_tmpl.c:156-167
-__device__ __forceinline__ int sample_lut(const int16_t *lut, const int randval, const int subx, const int suby,
-                                          const int bx, const int by, const int x, const int y)
-{
-    const int offx = 3 + (2 >> subx) * (3 + (randval >> 4));
-    const int offy = 3 + (2 >> suby) * (3 + (randval & 0xF));
-    return lut[(offy + y + (32 >> suby) * by) * GW + offx + x + (32 >> subx) * bx];
-}
 
 // Per-block random offsets (src/filmgrain_tmpl.c:192-214): block bx of block row r uses the (bx+1)-th output of an LFSR
 // seeded from r.  One lane walks one row's sequence once; the blocks then look their offsets up instead of each
@@ -395,20 +371,6 @@ __global__ __launch_bounds__(256) void fg_apply_kernel(const DevPlanes dst, cons
     }
 }
 
-FgParams make_params(const Dav1dHipFilmGrainData *d) {
-    FgParams p;
-    memset(&p, 0, sizeof(p));
-    p.seed = d->seed; p.num_y_points = d->num_y_points; p.chroma_scaling_from_luma = d->chroma_scaling_from_luma;
-    p.scaling_shift = d->scaling_shift; p.ar_coeff_lag = d->ar_coeff_lag; p.ar_coeff_shift = (int) d->ar_coeff_shift;
-    p.grain_scale_shift = d->grain_scale_shift; p.overlap_flag = d->overlap_flag; p.clip_to_restricted_range = d->clip_to_restricted_range;
-    for (int i = 0; i < 2; i++) {
-        p.num_uv_points[i] = d->num_uv_points[i];
-        p.uv_mult[i] = d->uv_mult[i]; p.uv_luma_mult[i] = d->uv_luma_mult[i]; p.uv_offset[i] = d->uv_offset[i];
-        memcpy(p.ar_coeffs_uv[i], d->ar_coeffs_uv[i], 28);
-    }
-    memcpy(p.ar_coeffs_y, d->ar_coeffs_y, 24);
-    return p;
-}
 
 } // namespace
 
@@ -424,6 +386,13 @@ extern "C" int dav1d_hip_launch_fg_gen(int16_t *luts, const Dav1dHipFilmGrainDat
 extern "C" int dav1d_hip_launch_fg_gen_part(int16_t *luts, const Dav1dHipFilmGrainData *data, int bpc, int layout, int part, void *stream)
 {
     hipLaunchKernelGGL(fg_gen_kernel, dim3(1), dim3(64), 0, (hipStream_t) stream, luts, make_params(data), layout, bpc - 8, part);
+    return hip_rc(hipGetLastError());
+}
+
+// the table alone, for a caller that keeps it (surface_grain.hip): rows 0 .. nrows - 1, nblk blocks each
+extern "C" int dav1d_hip_launch_fg_offsets(uint8_t *offs, unsigned seed, int nrows, int nblk, void *stream)
+{
+    hipLaunchKernelGGL(fg_offsets_kernel, dim3((nrows + 63) / 64), dim3(64), 0, (hipStream_t) stream, offs, seed, 0, nrows, nblk);
     return hip_rc(hipGetLastError());
 }
 

@@ -66,6 +66,9 @@ typedef struct Hip {
     int (*picture_free)(Dav1dHipContext *, Dav1dHipPicture *);
     int (*plane_download)(Dav1dHipContext *, const Dav1dHipPicture *, int, void *, ptrdiff_t, int);
     int (*surface_export)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, int, int);
+    int (*surface_export_grain)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipGrain *, int, int, int);
+    int (*fg_prepare)(Dav1dHipContext *, Dav1dHipGrain **, const Dav1dHipFilmGrainData *, int, int);
+    void (*fg_grain_destroy)(Dav1dHipContext *, Dav1dHipGrain *);
     int (*frame_set_progress_callback)(Dav1dHipFrame *, void (*)(void *, int, const Dav1dHipPicture *), void *);
     int (*live_objects)(long long *);
     int (*device_count)(void);
@@ -680,9 +683,10 @@ int dav1d_hip_glue_output_with_grain(Dav1dHipGlue *const g, const Dav1dPicture *
 }
 
 /* The same way out, staying on the device: the picture (with its grain, when asked for and the frame header carries any) into a surface the
- * caller owns, on the output context of the device the pixels live on.  Waits for the export, because the temporary picture of the grain goes
- * away here.  The harness that drives this binding has no device consumer, so this function is proven to compile and link by the hooked build
- * (-Wall) and its two library calls are tested in this order at the C ABI (tests/test_surface.py, test_grain_then_export). */
+ * caller owns, on the output context of the device the pixels live on.  Grain is applied by the export itself (dav1d_hip_surface_export_grain): no
+ * temporary picture, and the reference picture hp->ref stays what it was — a picture that lives in its twin is read from there.  Waits for the
+ * export, because the grain handle goes away here.  The harness that drives this binding has no device consumer, so this function is proven to
+ * compile and link by the hooked build (-Wall); the library calls behind it are tested at the C ABI (tests/test_surface_grain.py). */
 int dav1d_hip_glue_output_surface(Dav1dHipGlue *const g, const Dav1dPicture *const pic, const Dav1dHipSurface *const dst, const int apply_grain) {
     if (!g || !pic || !pic->allocator_data || !dst) return DAV1D_ERR(EINVAL);
     const Dav1dHipGluePicture *const hp = pic->allocator_data;
@@ -690,20 +694,19 @@ int dav1d_hip_glue_output_surface(Dav1dHipGlue *const g, const Dav1dPicture *con
     /* has_grain(), src/lib.c:303-309 */
     const int grain_here = apply_grain && (fg->num_y_points || fg->num_uv_points[0] || fg->num_uv_points[1] ||
                                            (fg->clip_to_restricted_range && fg->chroma_scaling_from_luma));
-    Dav1dHipPicture grain;
-    memset(&grain, 0, sizeof(grain));
+    Dav1dHipGrain *grain = NULL;
     Dav1dHipContext *const ctx_out = g->dev[hp->ref_dev].ctx_out;
     const int thread_dev = borrow_thread(g, ctx_out);
     int rc = 0;
     if (grain_here) {
-        rc = g->hip.picture_alloc(ctx_out, &grain, pic->p.w, pic->p.h, pic->p.layout, pic->p.bpc);
-        if (rc) { return_thread(g, thread_dev); return DAV1D_ERR(ENOMEM); }
-        rc = g->hip.fg_apply(ctx_out, &grain, &hp->ref, (const Dav1dHipFilmGrainData *) fg, pic->seq_hdr->mtrx == DAV1D_MC_IDENTITY);
-    }
-    if (!rc) rc = g->hip.surface_export(ctx_out, dst, grain_here ? &grain : &hp->ref, 0, pic->p.h);
+        rc = g->hip.fg_prepare(ctx_out, &grain, (const Dav1dHipFilmGrainData *) fg, pic->p.bpc, pic->p.layout);   /* layouts share their values */
+        if (rc) { return_thread(g, thread_dev); return rc == -ENOMEM ? DAV1D_ERR(ENOMEM) : DAV1D_ERR(EIO); }
+        rc = g->hip.surface_export_grain(ctx_out, dst, &hp->ref, grain, pic->seq_hdr->mtrx == DAV1D_MC_IDENTITY, 0, pic->p.h);
+    } else
+        rc = g->hip.surface_export(ctx_out, dst, &hp->ref, 0, pic->p.h);
     const int bad_args = rc == -EINVAL || rc == -ENOTSUP;
     if (!rc) rc = g->hip.sync(ctx_out);
-    if (grain_here) g->hip.picture_free(ctx_out, &grain);
+    if (grain) g->hip.fg_grain_destroy(ctx_out, grain);
     return_thread(g, thread_dev);
     return !rc ? 0 : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
 }
@@ -745,7 +748,8 @@ int dav1d_hip_glue_create(Dav1dHipGlue **const out, const Dav1dHipGlueOptions *c
     SYM(lister_const_masks, "dav1d_hip_lister_const_masks"); SYM(lister_destroy, "dav1d_hip_lister_destroy");
     SYM(frame_submit_intra_step, "dav1d_hip_frame_submit_intra_step"); SYM(frame_set_super_res, "dav1d_hip_frame_set_super_res");
     SYM(fg_apply, "dav1d_hip_fg_apply"); SYM(picture_alloc, "dav1d_hip_picture_alloc"); SYM(picture_free, "dav1d_hip_picture_free");
-    SYM(plane_download, "dav1d_hip_plane_download"); SYM(surface_export, "dav1d_hip_surface_export"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
+    SYM(plane_download, "dav1d_hip_plane_download"); SYM(surface_export, "dav1d_hip_surface_export"); SYM(surface_export_grain, "dav1d_hip_surface_export_grain");
+    SYM(fg_prepare, "dav1d_hip_fg_prepare"); SYM(fg_grain_destroy, "dav1d_hip_fg_grain_destroy"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
     SYM(live_objects, "dav1d_hip_live_objects"); SYM(device_count, "dav1d_hip_device_count"); SYM(use, "dav1d_hip_context_use");
     SYM(enable_peer_access, "dav1d_hip_enable_peer_access"); SYM(current_device, "dav1d_hip_current_device"); SYM(set_device, "dav1d_hip_set_device");
     SYM(picture_copy_peer, "dav1d_hip_picture_copy_peer"); SYM(picture_copy_peer_rows, "dav1d_hip_picture_copy_peer_rows"); SYM(picture_retile, "dav1d_hip_picture_retile");

@@ -250,6 +250,21 @@ typedef struct Dav1dHipSurface {
     int full_range;       /* RGB only: color_range */
 } Dav1dHipSurface;
 DAV1D_HIP_API int dav1d_hip_surface_export(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, int row0, int row1);
+/* The same export with film grain applied on the way (dav1d_amd/csrc/surface_grain.hip): writes byte for byte what dav1d_hip_surface_export(c, dst, G,
+ * row0, row1) writes, G being the picture dav1d_hip_fg_apply_prepared(c, G, src, grain, is_id) produces — without G: one pass over the source, no
+ * temporary picture, no allocation of a picture, no host wait.  `src` is const: a DAV1D_HIP_TWIN_ONLY picture is read from its twin and stays what it
+ * was (dav1d_hip_fg_apply* un-tile such a source; this call does not).  `grain` is a handle of dav1d_hip_fg_prepare for the picture's bpc and layout; the
+ * call waits for its templates on the context's stream as dav1d_hip_fg_apply_prepared does.  Asynchronous exactly like dav1d_hip_surface_export: it
+ * returns at once, dav1d_hip_sync waits, dav1d_hip_last_kernel_ms reports its device time.  The per-block random offsets of the picture's geometry
+ * (ceil(w / 32) * ceil(h / 32) bytes) are tabulated into the HANDLE on the context's stream the first time a geometry is seen and live until
+ * dav1d_hip_fg_grain_destroy: a handle serves one context at a time, and calls on one handle come from one thread at a time.
+ * Rows as above; grain of a row depends on that row only (and on the luma row above a chroma row), so bands need not align with the 32-row grain
+ * blocks and give the bytes of one whole-picture call.  A handle whose parameters give no plane of the picture any grain: the plain export.
+ * Errors, before anything is enqueued: everything dav1d_hip_surface_export refuses, with its code; -EINVAL for a NULL handle or one prepared for
+ * another bpc or layout. */
+typedef struct Dav1dHipGrain Dav1dHipGrain;
+DAV1D_HIP_API int dav1d_hip_surface_export_grain(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                 const Dav1dHipGrain *grain, int is_id, int row0, int row1);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,
@@ -747,7 +762,6 @@ DAV1D_HIP_API int dav1d_hip_fg_apply(Dav1dHipContext *c, const Dav1dHipPicture *
  * templates and scaling tables depend on the frame header only, so dav1d_hip_fg_prepare can be called as soon as the header is
  * parsed — it enqueues their generation on a side stream and returns — and dav1d_hip_fg_apply_prepared, at the end of the
  * frame, only waits for that event.  The ~0.23 ms the lone-wave template kernels take then hide behind the reconstruction. */
-typedef struct Dav1dHipGrain Dav1dHipGrain;
 DAV1D_HIP_API int dav1d_hip_fg_prepare(Dav1dHipContext *c, Dav1dHipGrain **out, const Dav1dHipFilmGrainData *data, int bpc, int layout);
 DAV1D_HIP_API int dav1d_hip_fg_apply_prepared(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *src,
                                               const Dav1dHipGrain *g, int is_id);

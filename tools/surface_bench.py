@@ -2,12 +2,15 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
 everything repeated `repeats` times to show the spread.  Bytes per call come from the shapes (bytes read + bytes written).  The host
 fetch (dav1d_hip_host_picture_fetch + _wait) is printed for orientation only: it crosses PCIe and is no peer of a device-to-device pass.
+--grain: the export with film grain fused in (dav1d_hip_surface_export_grain: planar native, P010, RGB native; from twin-only and from raster
+sources; luma + both chroma planes, overlap on) against the sequence it replaces, timed the same way in the same run: dav1d_hip_fg_apply_prepared
+into a pre-allocated picture, then dav1d_hip_surface_export from that, on sources with valid raster planes (its best case: no un-tile).
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -44,9 +47,90 @@ class Events:
         return ms.value
 
 
+def grain_data():
+    """luma + both chroma planes, overlap on; fixed so that runs compare"""
+    from dav1d_amd._lib import FilmGrainData
+    d = FilmGrainData()
+    d.seed = 1234
+    d.num_y_points = 2
+    d.y_points[0][0], d.y_points[0][1], d.y_points[1][0], d.y_points[1][1] = 0, 40, 255, 120
+    for pl in range(2):
+        d.num_uv_points[pl] = 2
+        d.uv_points[pl][0][0], d.uv_points[pl][0][1], d.uv_points[pl][1][0], d.uv_points[pl][1][1] = 0, 30, 255, 90
+        d.uv_mult[pl], d.uv_luma_mult[pl], d.uv_offset[pl] = 64, 32, 0
+        for i in range(25):
+            d.ar_coeffs_uv[pl][i] = (i % 5) - 2
+    for i in range(24):
+        d.ar_coeffs_y[i] = (i % 7) - 3
+    d.scaling_shift, d.ar_coeff_lag, d.ar_coeff_shift, d.grain_scale_shift = 9, 3, 7, 0
+    d.overlap_flag, d.clip_to_restricted_range = 1, 1
+    return d
+
+
+def grain_runs(a, ctx, ev, pics, variants, src_bytes):
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    handle = ctx.fg_prepare(grain_data(), bpc, layout)
+    tmps = [ctx.picture(w, h, layout, bpc) for _ in range(a.pairs)]
+    ctx.sync()
+    runs, all_surfs = [], []
+    for name, fmt, sample, out_bytes in variants:
+        surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
+        all_surfs += surfs
+
+        def two_calls(k, surfs=surfs):
+            p, t = pics[k % a.pairs], tmps[k % a.pairs]
+            p.pic.twin_ok = 1                  # raster planes and twin agree: nothing to un-tile
+            ctx.fg_apply_prepared(t, p, handle)
+            t.export(surfs[k % a.pairs])
+
+        def fused(k, surfs=surfs, state=api.TWIN_ONLY):
+            p = pics[k % a.pairs]
+            p.pic.twin_ok = state
+            p.export(surfs[k % a.pairs], grain=handle)
+        # the two calls read the source (and the luma again under the chroma), write the picture, read it, write the surface
+        runs.append(("fg_apply_prepared + export: " + name, 3 * src_bytes + 2 * w * h + out_bytes, two_calls, None))
+        yard = runs[-1][0]
+        luma_again = 0 if fmt == api.SURFACE_RGB_PLANAR else 2 * w * ((h + 1) // 2)      # the one extra read: the luma rows under the chroma rows
+        runs.append(("fused, twin-only source: " + name, src_bytes + luma_again + out_bytes, fused, yard))
+        runs.append(("fused, raster source: " + name, src_bytes + luma_again + out_bytes, lambda k, f=fused: f(k, state=0), yard))
+    print("# surface_bench --grain on %s: %dx%d 4:2:0 %d-bit, %d picture / surface pairs in rotation, 20 warm-up + %d timed calls per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, a.pairs, a.calls, a.repeats))
+    print("# bytes per call = bytes read + bytes written, from the shapes (templates, tables and offsets not counted)")
+    results = {r[0]: [] for r in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, call, _ in runs:
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            print("repeat %d  %-62s %8.4f ms/call  %7.1f MB/call  %7.0f GB/s" % (rep, name, ms, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (min / median / max ms per call over the repeats)")
+    for name, nbytes, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-62s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(results[name]), sorted(results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-62s median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms: %s"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met"))
+    ctx.fg_grain_destroy(handle)
+    for s in all_surfs:
+        s.free()
+    for p in tmps + pics:
+        p.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
+    ap.add_argument("--grain", action="store_true", help="the fused grain + export variants against fg_apply_prepared + export")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -76,6 +160,8 @@ def main():
                 ("RGB planar native BT.709 limited", R, api.SAMPLE_NATIVE, 3 * 2 * w * h), ("RGB planar float32 BT.709 limited", R, api.SAMPLE_F32, 3 * 4 * w * h)]
     if a.short:
         variants = variants[:3]
+    if a.grain:
+        return grain_runs(a, ctx, ev, pics, variants[:3], src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
