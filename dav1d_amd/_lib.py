@@ -28,6 +28,10 @@ class Surface(C.Structure):            # == Dav1dHipSurface
                 ("matrix", C.c_int), ("full_range", C.c_int)]
 
 
+class SurfaceRect(C.Structure):        # == Dav1dHipSurfaceRect
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
 class HostPicture(C.Structure):
     _fields_ = [("data", C.c_void_p * 3), ("stride", C.c_ssize_t * 2), ("dev", Picture), ("alloc", C.c_void_p), ("alloc_size", C.c_size_t)]
 
@@ -85,7 +89,7 @@ SYMBOLS = [
     "dav1d_hip_lister_create", "dav1d_hip_lister_tile_sbrow", "dav1d_hip_lister_run", "dav1d_hip_lister_filter_run", "dav1d_hip_lister_run_frame", "dav1d_hip_lister_prep_elems", "dav1d_hip_lister_mask_bytes",
     "dav1d_hip_lister_steps", "dav1d_hip_lister_const_masks", "dav1d_hip_lister_destroy",
     "dav1d_hip_lister_mask_offset", "dav1d_hip_lister_tables", "dav1d_hip_lister_block_warp", "dav1d_hip_lister_filter_sbrow",
-    "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain",
+    "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain", "dav1d_hip_surface_export_scaled", "dav1d_hip_surface_scaled_rows_needed",
 ]
 
 
@@ -286,6 +290,8 @@ def load(path=None):
         "dav1d_hip_enable_peer_access": (i, [vp, vp]),
         "dav1d_hip_surface_export": (i, [vp, P(Surface), P(Picture), i, i]),
         "dav1d_hip_surface_export_grain": (i, [vp, P(Surface), P(Picture), vp, i, i, i]),
+        "dav1d_hip_surface_export_scaled": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), i, i]),
+        "dav1d_hip_surface_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), i]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

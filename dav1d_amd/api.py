@@ -11,6 +11,7 @@ from . import _lib
 from ._lib import FilmGrainData  # noqa: F401
 from ._lib import ITX_TASK, MC_TASK, COMP_TASK, CDEF_TASK, LF_TASK, IPRED_TASK, LR_TASK, WARP_TASK, MC_SCALED_TASK, Picture, HostPicture  # noqa: F401  (re-exported)
 from ._lib import Surface as SurfaceDesc
+from ._lib import SurfaceRect
 
 LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
 SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR = 0, 1, 2      # enum Dav1dHipSurfaceFormat
@@ -127,6 +128,22 @@ class DevicePicture:
             return
         _chk(self.ctx.lib.dav1d_hip_surface_export(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), row0, row1), "surface_export")
 
+    @staticmethod
+    def _rect(crop):
+        return None if crop is None else C.byref(SurfaceRect(*[int(v) for v in crop]))
+
+    def export_scaled(self, surface, crop=None, row0=0, row1=1 << 30):
+        """dav1d_hip_surface_export_scaled: the rectangle crop = (x0, y0, w, h) of this picture (None: all of it), scaled down to the surface's
+        own size by the area scaler of include/dav1d_hip.h, into DESTINATION luma rows [row0, row1) of the surface.  Asynchronous like export."""
+        _chk(self.ctx.lib.dav1d_hip_surface_export_scaled(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), row0, row1),
+             "surface_export_scaled")
+
+    def scaled_rows_needed(self, surface, crop, row1):
+        """dav1d_hip_surface_scaled_rows_needed: the source luma rows, from the top, that destination rows [0, row1) of export_scaled read"""
+        n = self.ctx.lib.dav1d_hip_surface_scaled_rows_needed(C.byref(surface.desc), C.byref(self.pic), self._rect(crop), row1)
+        _chk(min(n, 0), "surface_scaled_rows_needed")
+        return n
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -208,13 +225,19 @@ class Surface:
         self.bufs = None
 
 
-def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0):
+def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0, crop=None, resize=False):
     """Fills torch tensors on the picture's device through tensor.data_ptr(): `tensor` of shape (3, h, w) gets R, G, B planes; with
     `chroma` of shape (ceil(h / 2), 2 * ceil(w / 2)) given, `tensor` (h, w) gets luma and `chroma` the interleaved U, V of a 4:2:0
     picture (NV12 / P010 family).  The sample type follows the dtype (float32: F32; else `sample`, native by default).  The context should
     have been opened on the stream the tensors are used on (api.Context(stream=torch.cuda.current_stream().cuda_stream)).  `grain` / `is_id`:
-    as in DevicePicture.export."""
+    as in DevicePicture.export.  `resize=True`: the tensors' shape gives the output size, and `crop` = (x0, y0, w, h) (None: the whole picture)
+    the rectangle that is scaled to it (DevicePicture.export_scaled; rows are then destination rows, and there is no grain)."""
     import torch
+    if crop is not None and not resize:
+        raise ValueError("crop= needs resize=True")
+    if resize and grain is not None:
+        raise ValueError("the scaled export applies no film grain")
+    w, h = (int(tensor.shape[-1]), int(tensor.shape[-2])) if resize else (pic.w, pic.h)
     ts = [tensor] if chroma is None else [tensor, chroma]
     for t in ts:
         if not t.is_cuda or t.stride(-1) != 1:
@@ -223,20 +246,23 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
         sample = SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_NATIVE
     es = tensor.element_size()
     if chroma is None:
-        if tuple(tensor.shape) != (3, pic.h, pic.w):
+        if tuple(tensor.shape) != (3, h, w):
             raise ValueError("an RGB tensor has shape (3, h, w)")
         fmt = SURFACE_RGB_PLANAR
         ptrs = [tensor[k].data_ptr() for k in range(3)]
         strides = [tensor.stride(1) * es] * 3
     else:
-        if tuple(tensor.shape) != (pic.h, pic.w) or chroma.dtype != tensor.dtype:
+        if tuple(tensor.shape) != (h, w) or chroma.dtype != tensor.dtype:
             raise ValueError("a semi-planar pair has shapes (h, w) and (ceil(h / 2), 2 * ceil(w / 2)) and one dtype")
         fmt = SURFACE_SEMIPLANAR
         ptrs = [tensor.data_ptr(), chroma.data_ptr()]
         strides = [tensor.stride(0) * es, chroma.stride(0) * es]
-    s = Surface.wrap(pic.ctx, ptrs, strides, pic.w, pic.h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
+    s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
     if s.dtype.itemsize != es or [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]:
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
+    if resize:
+        pic.export_scaled(s, crop, row0, row1)
+        return s
     pic.export(s, row0, row1, grain=grain, is_id=is_id)
     return s
 

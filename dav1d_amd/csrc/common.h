@@ -161,6 +161,16 @@ __device__ __forceinline__ unsigned mul_u24(unsigned a, unsigned b) {
     return r;
 #endif
 }
+__device__ __forceinline__ unsigned mad_u24(unsigned a, unsigned b, unsigned c) {      // a * b + c (v_mad_u32_u24), the sum modulo 2^32
+#ifdef DAV1D_HIP_EMU
+    if (a >= (1u << 24) || b >= (1u << 24)) __builtin_trap();
+    return a * b + c;
+#else
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+#endif
+}
 __device__ __forceinline__ uint32_t rep2(int v) {                     // the same value in both halves
 #ifdef DAV1D_HIP_EMU
     return (uint32_t) (v & 0xffff) * 0x10001u;

@@ -1,4 +1,5 @@
-// What the two output units share (surface.hip: the plain export; surface_grain.hip: the export with film grain fused in): the 8-sample unit and
+// What the output units share (surface.hip: the plain export; surface_grain.hip: the export with film grain fused in; surface_scale.hip: the export
+// with a crop and a scaler in front): the 8-sample unit and
 // its loads and stores, the output sample functors, the kernel arguments and how a call is checked and turned into them.  See surface.hip for the
 // layout of a wave (8 rows x 8 units, a 64 x 8 cell of a plane).
 #pragma once
@@ -159,23 +160,27 @@ struct SurfaceCall {
     void *planes[3];
 };
 
-inline int surface_call_check(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, int row0, int row1, SurfaceCall *const call)
+// (`scaled`: the surface has a size of its own, dav1d_hip_surface_export_scaled — the size rule falls away, its planes and rows are the surface's)
+inline int surface_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, int row0, int row1, SurfaceCall *const call, const bool scaled)
 {
-    if (!c || !dst || !src || !src->p[0].data) return -EINVAL;
+    if (!dst || !src || !src->p[0].data) return -EINVAL;
     if (src->bpc != 8 && src->bpc != 10 && src->bpc != 12) return -EINVAL;
     if (src->layout < DAV1D_HIP_LAYOUT_I400 || src->layout > DAV1D_HIP_LAYOUT_I444) return -EINVAL;
     if (dst->format < DAV1D_HIP_SURFACE_PLANAR || dst->format > DAV1D_HIP_SURFACE_RGB_PLANAR) return -EINVAL;
     if (dst->sample < DAV1D_HIP_SAMPLE_NATIVE || dst->sample > DAV1D_HIP_SAMPLE_F32) return -EINVAL;
     if (dst->sample == DAV1D_HIP_SAMPLE_MSB16 && src->bpc == 8) return -EINVAL;
     const int w = src->p[0].w, h = src->p[0].h;
-    if (w <= 0 || h <= 0 || dst->w != w || dst->h != h) return -EINVAL;
+    if (w <= 0 || h <= 0) return -EINVAL;
+    if (scaled ? dst->w <= 0 || dst->h <= 0 : dst->w != w || dst->h != h) return -EINVAL;
     const int mono = src->layout == DAV1D_HIP_LAYOUT_I400;
+    const int ss_hor = !mono && src->layout != DAV1D_HIP_LAYOUT_I444, dw = dst->w, dh = dst->h;
     if (!mono && (!src->p[1].data || !src->p[2].data)) return -EINVAL;
     const ptrdiff_t ss = dst->sample == DAV1D_HIP_SAMPLE_F32 ? 4 : dst->sample == DAV1D_HIP_SAMPLE_MSB16 ? 2 : src->bpc > 8 ? 2 : 1;
     const bool rgb = dst->format == DAV1D_HIP_SURFACE_RGB_PLANAR;
     const int n_dst = rgb ? 3 : mono ? 1 : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 : 3;
     for (int k = 0; k < n_dst; k++) {
-        const ptrdiff_t row_bytes = ss * (rgb || !k ? w : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 * src->p[1].w : src->p[k].w);
+        const int cw = scaled ? (dw + ss_hor) >> ss_hor : src->p[k].w;
+        const ptrdiff_t row_bytes = ss * (rgb || !k ? dw : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 * cw : cw);
         if (!dst->data[k] || dst->stride[k] < row_bytes || dst->stride[k] % ss) return -EINVAL;
     }
     if (rgb) {
@@ -183,8 +188,8 @@ inline int surface_call_check(Dav1dHipContext *const c, const Dav1dHipSurface *c
         else if (dst->matrix != 1 && dst->matrix != 5 && dst->matrix != 6 && dst->matrix != 9) return -ENOTSUP;
     }
     if (row0 < 0) row0 = 0;
-    if (row1 > h) row1 = h;
-    if ((row0 & 1) || ((row1 & 1) && row1 < h)) return -EINVAL;       // a chroma row belongs to one band
+    if (row1 > dh) row1 = dh;
+    if ((row0 & 1) || ((row1 & 1) && row1 < dh)) return -EINVAL;      // a chroma row belongs to one band
     call->row0 = row0; call->row1 = row1;
     call->tiled = src->twin_ok == DAV1D_HIP_TWIN_ONLY;
     for (int pl = 0; pl < 3; pl++) {
@@ -192,6 +197,13 @@ inline int surface_call_check(Dav1dHipContext *const c, const Dav1dHipSurface *c
         if ((!pl || !mono) && (!call->planes[pl] || src->p[pl].stride <= 0)) return -EINVAL;
         if ((!pl || !mono) && call->tiled && (src->p[pl].stride / (src->bpc > 8 ? 2 : 1)) % 8) return -EINVAL;
     }
+    return 0;
+}
+inline int surface_call_check(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const int row0, const int row1,
+                              SurfaceCall *const call, const bool scaled = false)
+{
+    if (!c) return -EINVAL;
+    if (const int rc = surface_args_check(dst, src, row0, row1, call, scaled)) return rc;
     return pictures_on_device(c, src, 1);
 }
 
@@ -208,6 +220,19 @@ inline SurfaceGeom surface_geom(const Dav1dHipPicture *const src, const int row0
     g.cw = g.mono ? g.w : src->p[1].w; g.ch = g.mono ? g.h : src->p[1].h;
     g.crow0 = row0 >> g.ss_ver; g.crow1 = row1 >= g.h ? g.ch : row1 >> g.ss_ver;
     return g;
+}
+
+// the colour part of the arguments: the row of rgb_coef the surface asks for
+inline void rgb_set_matrix(RgbArgs &a, const Dav1dHipSurface *const dst, const int bpc, const int mono)
+{
+    a.mid = 1 << (bpc - 1); a.max = (1 << bpc) - 1;
+    a.identity = dst->matrix == 0; a.mono = mono;
+    if (!a.identity) {
+        const int m = dst->matrix == 1 ? 0 : dst->matrix == 9 ? 2 : 1;
+        const int *const k = rgb_coef[m][!!dst->full_range][(bpc - 8) >> 1];
+        a.cy = k[0]; a.crv = k[1]; a.cbu = k[2]; a.cgu = k[3]; a.cgv = k[4];
+        a.yoff = dst->full_range ? 0 : 16 << (bpc - 8);
+    }
 }
 
 // RGB: the kernel's arguments; *n_cells = the 64 x 8 chroma cells of the call (a wave each)
@@ -228,14 +253,7 @@ RgbArgs make_rgb_args(const Dav1dHipSurface *const dst, const Dav1dHipPicture *c
     for (int pl = 0; pl < 3; pl++) a.dwide &= aligned_to(dst->data[pl], dst->stride[pl], store_align);
     a.w = g.w; a.cw = g.cw; a.row1 = row1; a.crow0 = g.crow0; a.crow1 = g.crow1;
     a.n_cx = (g.cw + 63) / 64;
-    a.mid = 1 << (src->bpc - 1); a.max = (1 << src->bpc) - 1;
-    a.identity = dst->matrix == 0; a.mono = g.mono;
-    if (!a.identity) {
-        const int m = dst->matrix == 1 ? 0 : dst->matrix == 9 ? 2 : 1;
-        const int *const k = rgb_coef[m][!!dst->full_range][(src->bpc - 8) >> 1];
-        a.cy = k[0]; a.crv = k[1]; a.cbu = k[2]; a.cgu = k[3]; a.cgv = k[4];
-        a.yoff = dst->full_range ? 0 : 16 << (src->bpc - 8);
-    }
+    rgb_set_matrix(a, dst, src->bpc, g.mono);
     const int n_cy = ((g.crow1 + 7) >> 3) - (g.crow0 >> 3);
     *n_cells = (unsigned) a.n_cx * (unsigned) n_cy;
     return a;

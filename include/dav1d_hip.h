@@ -245,7 +245,7 @@ typedef struct Dav1dHipSurface {
     void *data[3];        /* DEVICE memory of the caller (dav1d_hip_malloc, a torch tensor, ...) on the context's device */
     ptrdiff_t stride[3];  /* bytes; any multiple of the sample size >= the row's bytes (tight rows included) */
     int format, sample;   /* enum Dav1dHipSurfaceFormat, enum Dav1dHipSurfaceSample */
-    int w, h;             /* must equal the picture's visible luma size */
+    int w, h;             /* must equal the picture's visible luma size (dav1d_hip_surface_export_scaled: the output size) */
     int matrix;           /* RGB only: AV1 matrix_coefficients (0 identity, 1 BT.709, 5 / 6 BT.601, 9 BT.2020 NCL) */
     int full_range;       /* RGB only: color_range */
 } Dav1dHipSurface;
@@ -265,6 +265,33 @@ DAV1D_HIP_API int dav1d_hip_surface_export(Dav1dHipContext *c, const Dav1dHipSur
 typedef struct Dav1dHipGrain Dav1dHipGrain;
 DAV1D_HIP_API int dav1d_hip_surface_export_grain(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
                                                  const Dav1dHipGrain *grain, int is_id, int row0, int row1);
+/* The same export through a crop and a scaler (dav1d_amd/csrc/surface_scale.hip): dst->w x dst->h is the OUTPUT size, `crop` (NULL: the whole picture)
+ * the rectangle of the visible picture that is scaled to it; x0 is even where the layout is subsampled across, y0 where it is subsampled down.  The call
+ * writes byte for byte what dav1d_hip_surface_export would write from a picture whose planes are the scaled planes: for plane pl with (ssh, ssv) the
+ * window at (x0 >> ssh, y0 >> ssv) of size ((w + ssh) >> ssh, (h + ssv) >> ssv) goes through S to ((dst->w + ssh) >> ssh, (dst->h + ssv) >> ssv), every
+ * plane on its own; RGB is the formula above applied to the scaled Y, U, V.
+ * S(P, sw, sh, dw, dh), 1 <= dw <= sw <= 8 dw and 1 <= dh <= sh <= 8 dh: area averaging with 12-bit weights, separable, the vertical pass first.
+ * Per axis (source length s, destination length d), output o covers [o s, (o + 1) s) in units of 1 / d of a source sample and source sample i covers
+ * [i d, (i + 1) d); its taps are i0 = (o s) / d .. i1 = ((o + 1) s + d - 1) / d - 1 (at most 9); with the cumulative coverage
+ * C_k = min((o + 1) s, (k + 1) d) - o s (C_{i0 - 1} = 0) and q(C) = (C * 4096 + s / 2) / s the weight of tap k is w_k = q(C_k) - q(C_{k - 1}): never
+ * negative, 4096 in sum.  Then t[x] = (sum_j wy_j P[y_j][x] + 8) >> 4 (below 2^20) and out = (sum_i wx_i t[x_i] + (1 << 19)) >> 20 in uint32 (the
+ * sum stays below 2^32).  No clip is needed; a constant plane stays constant; d == s returns the samples; an exact 2:1 in both axes is
+ * (a + b + c + d + 2) >> 2.  DESIGN.md 10.2.
+ * [drow0, drow1) are DESTINATION luma rows (clamped to the surface; both multiples of 2 unless they are the surface's end), the chroma rows under them
+ * follow as above.  Asynchronous exactly like dav1d_hip_surface_export: one launch on the context's stream, dav1d_hip_last_kernel_ms reports its device
+ * time, `src` is const and a DAV1D_HIP_TWIN_ONLY picture stays one, nothing is written outside the visible destination samples of the rows asked for; no
+ * host allocation and no host wait (the weights are computed in the kernel).
+ * Errors, before anything is enqueued: everything dav1d_hip_surface_export refuses, with its code, except the size rule; -EINVAL for a crop outside the
+ * picture, an empty crop, an odd x0 / y0 where the layout subsamples that axis, odd band rows; -ENOTSUP for dst->w > w, dst->h > h, w > 8 dst->w,
+ * h > 8 dst->h (upscaling and ratios above 8 are not built).
+ * dav1d_hip_surface_scaled_rows_needed is host arithmetic: the number of source luma rows, counted from the top of the picture, that must be complete
+ * before destination rows [0, drow1) can be exported — the maximum over luma and chroma of y0 + ceil(r1 sh / dh), chroma shifted up by ss_ver, clamped
+ * to the picture's height — so that an application can follow dav1d_hip_frame_set_progress_callback band by band; a negative errno for what the export
+ * would refuse. */
+typedef struct Dav1dHipSurfaceRect { int x0, y0, w, h; } Dav1dHipSurfaceRect;
+DAV1D_HIP_API int dav1d_hip_surface_export_scaled(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                  const Dav1dHipSurfaceRect *crop, int drow0, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_scaled_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop, int drow1);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -11,6 +11,9 @@ fetch (dav1d_hip_host_picture_fetch + _wait) is printed for orientation only: it
 --grain: the export with film grain fused in (dav1d_hip_surface_export_grain: planar native, P010, RGB native; from twin-only and from raster
 sources; luma + both chroma planes, overlap on) against the sequence it replaces, timed the same way in the same run: dav1d_hip_fg_apply_prepared
 into a pre-allocated picture, then dav1d_hip_surface_export from that, on sources with valid raster planes (its best case: no un-tile).
+--scaled: dav1d_hip_surface_export_scaled at 2:1 (8K to 4K) and 4:1 (8K to 1080p) as planar native, P010 and RGB planar native, against the
+yardstick a user pays today before any scaler of their own runs: dav1d_hip_surface_export of the same picture at full size in the same format,
+timed the same way in the same run.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -127,10 +130,63 @@ def grain_runs(a, ctx, ev, pics, variants, src_bytes):
     ctx.close()
 
 
+def scaled_runs(a, ctx, ev, pics, variants, src_bytes):
+    """2:1 and 4:1 of every format against the plain export of the same picture at full size in the same format (the yardstick)"""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    runs, all_surfs = [], []
+    for name, fmt, sample, out_bytes in variants:
+        full = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
+        all_surfs += full
+
+        def plain(k, surfs=full):
+            pics[k % a.pairs].export(surfs[k % a.pairs])
+        runs.append(("export, full size: " + name, src_bytes + out_bytes, plain, None))
+        yard = runs[-1][0]
+        for ratio in (2, 4):
+            small = [ctx.surface(w // ratio, h // ratio, layout, bpc, fmt, sample) for _ in range(a.pairs)]
+            all_surfs += small
+
+            def scaled(k, surfs=small):
+                pics[k % a.pairs].export_scaled(surfs[k % a.pairs])
+            runs.append(("scaled %d:1 (%dx%d): %s" % (ratio, w // ratio, h // ratio, name), src_bytes + out_bytes // (ratio * ratio), scaled, yard))
+    print("# surface_bench --scaled on %s: %dx%d 4:2:0 %d-bit twin-only sources, %d picture / surface pairs in rotation, 20 warm-up + %d timed calls per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, a.pairs, a.calls, a.repeats))
+    print("# bytes per call = bytes read + bytes written, from the shapes")
+    results = {r[0]: [] for r in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, call, _ in runs:
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            print("repeat %d  %-62s %8.4f ms/call  %7.1f MB/call  %7.0f GB/s" % (rep, name, ms, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (min / median / max ms per call over the repeats)")
+    for name, nbytes, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-62s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(results[name]), sorted(results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-62s median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms: %s"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met"))
+    for s in all_surfs:
+        s.free()
+    for p in pics:
+        p.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
     ap.add_argument("--grain", action="store_true", help="the fused grain + export variants against fg_apply_prepared + export")
+    ap.add_argument("--scaled", action="store_true", help="dav1d_hip_surface_export_scaled at 2:1 and 4:1 against the plain export at full size")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -162,6 +218,8 @@ def main():
         variants = variants[:3]
     if a.grain:
         return grain_runs(a, ctx, ev, pics, variants[:3], src_bytes)
+    if a.scaled:
+        return scaled_runs(a, ctx, ev, pics, variants[:3], src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
