@@ -118,7 +118,6 @@ struct TaskBuf {
     TaskBuf &operator=(const TaskBuf &) = delete;
 };
 
-
 // brackets the launches of a batch call with events on the context's stream
 struct KernelTimer {
     Dav1dHipContext *c;
@@ -171,6 +170,30 @@ static inline int hip_rc(hipError_t e) {
 }
 #define HIP_TRY(x) do { const int rc_ = hip_rc(x); if (rc_) return rc_; } while (0)
 
+// Measurement aid behind the *_run_timed calls: N steps one after the other on the context's stream, each between two events.  step(k, cnt)
+// launches step k and says how much it holds (0 = it launched nothing); after the first step that fails nothing more is launched.  ms[k]: the
+// step's device time, 0 for a step that launched nothing; counts (may be NULL): cnt of every step that was reached.  Waits for the stream.
+template <int N, typename Step>
+static inline int timed_launches(Dav1dHipContext *c, float *ms, size_t *counts, Step step) {
+    hipEvent_t ev[N + 1];
+    bool ran[N];
+    for (int k = 0; k <= N; k++) {
+        const hipError_t e = hipEventCreate(&ev[k]);
+        if (e != hipSuccess) { while (k--) (void) hipEventDestroy(ev[k]); return hip_rc(e); }
+    }
+    int rc = hip_rc(hipEventRecord(ev[0], c->stream));
+    for (int k = 0; k < N; k++) {
+        size_t cnt = 0;
+        if (!rc) { rc = step(k, cnt); if (counts) counts[k] = cnt; }
+        ran[k] = cnt != 0;
+        (void) hipEventRecord(ev[k + 1], c->stream);
+    }
+    (void) hipStreamSynchronize(c->stream);
+    for (int k = 0; k < N; k++) { ms[k] = 0.f; if (ran[k]) (void) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]); }
+    for (int k = 0; k <= N; k++) (void) hipEventDestroy(ev[k]);
+    return rc;
+}
+
 static inline DevPlanes dev_planes(const Dav1dHipPicture *p) {
     DevPlanes d;
     const int bps = p->bpc > 8 ? 2 : 1;
@@ -183,6 +206,10 @@ static inline DevPlanes dev_planes(const Dav1dHipPicture *p) {
     d.tiled = 0;
     return d;
 }
+// Entry points that write (or read and write) the RASTER planes of `dst` refuse a picture that lives in its tiled twin only
+// (DAV1D_HIP_TWIN_ONLY): they would work on stale planes and leave the flag saying that the twin is the picture.  -EINVAL before anything is
+// enqueued; the caller un-tiles first (dav1d_hip_picture_untile) or writes through dav1d_hip_recon_list_run_tiled.
+static inline bool raster_dst_ok(const Dav1dHipPicture *dst) { return dst && dst->twin_ok != DAV1D_HIP_TWIN_ONLY; }
 static inline bool picture_twin_usable(const Dav1dHipPicture *p) {
     if (!p->twin_ok) return false;          // (1: twin and raster planes agree; DAV1D_HIP_TWIN_ONLY: the twin is the picture)
     const int bps = p->bpc > 8 ? 2 : 1;
@@ -190,6 +217,8 @@ static inline bool picture_twin_usable(const Dav1dHipPicture *p) {
         if (p->p[i].data && (!p->twin[i] || (p->p[i].stride / bps) % 8)) return false;
     return true;
 }
+// storage for a picture's tiled twin where it has none yet
+static inline int twin_on_demand(Dav1dHipContext *c, Dav1dHipPicture *pic) { return !pic->twin_alloc && !pic->twin[0] ? dav1d_hip_picture_twin_alloc(c, pic) : 0; }
 // Before a launch that reads RASTER planes of pictures: the ones that live in their twin only (DAV1D_HIP_TWIN_ONLY, what a
 // reconstruction in the tiled layout leaves) get their raster planes back first, on the context's stream — a raster reader of such a
 // picture would take stale pixels for the picture without any sign of it.  (The pictures are const for the caller's sake: their pixels do
@@ -219,6 +248,17 @@ static inline int ref_planes(Dav1dHipContext *c, const Dav1dHipPicture *refs, in
         }
     }
     return 0;
+}
+// What a launch that predicts from `refs` asks first: 1 .. 8 references, the list's highest index (max_ref) among them, dst's bit depth (dst NULL: not asked, the timed aids) ...
+static inline int refs_ok(const Dav1dHipPicture *dst, const Dav1dHipPicture *refs, int n_refs, int max_ref) {
+    if (n_refs < 1 || n_refs > 8 || max_ref >= n_refs) return -EINVAL;
+    for (int i = 0; i < n_refs && dst; i++) if (refs[i].bpc != dst->bpc) return -EINVAL;
+    return 0;
+}
+// ... and then their planes in rp[8] (ref_planes)
+static inline int checked_ref_planes(Dav1dHipContext *c, const Dav1dHipPicture *dst, const Dav1dHipPicture *refs, int n_refs, int max_ref, DevPlanes *rp) {
+    if (const int rc = refs_ok(dst, refs, n_refs, max_ref)) return rc;
+    return ref_planes(c, refs, n_refs, rp);
 }
 
 // kernel launchers (one per family translation unit)
@@ -391,7 +431,7 @@ extern "C" int dav1d_hip_launch_fg_apply(const DevPlanes *dst, const DevPlanes *
 
 extern "C" int dav1d_hip_launch_fg_offsets(uint8_t *offs, unsigned seed, int nrows, int nblk, void *stream);
 
-// Grain templates + scaling tables of one frame (dav1d_hip_fg_prepare, capi.hip), and the per-block random offsets of the picture geometries the
+// Grain templates + scaling tables of one frame (dav1d_hip_fg_prepare, api_batch.hip), and the per-block random offsets of the picture geometries the
 // fused export (surface_grain.hip) met: a table depends on the seed and the block counts only, is built on the context's stream the first time
 // its geometry is seen and lives until dav1d_hip_fg_grain_destroy, so a call that returns at once leaves nothing behind that could go away under
 // its kernels.  `offs` is the one part of a handle that changes after dav1d_hip_fg_prepare: a handle serves one context at a time.

@@ -19,7 +19,7 @@
 #include <unordered_map>
 #include <new>
 
-uint64_t dav1d_hip_mc_geo_sig(const DevPlanes *rp, int n_refs);       // capi.hip: the key mc_regroup() remembers a grouping by
+uint64_t dav1d_hip_mc_geo_sig(const DevPlanes *rp, int n_refs);       // api_lists.hip: the key mc_regroup() remembers a grouping by
 
 namespace {
 
@@ -188,7 +188,7 @@ struct HintScratch {
 inline int n_tiles(const int w, const int h) { return ((w + 63) >> 6) * ((h + 15) >> 4); }
 inline int bin_of(const int w, const int h) { return tile_dim_class(w < 64 ? w : 64) * 3 + tile_dim_class(h < 16 ? h : 16); }
 
-// mc_ref_of (capi.hip) in line: a million calls per 8K frame
+// mc_ref_of (api_lists.hip) in line: a million calls per 8K frame
 inline McRef ref_of(const Dav1dHipMcTask &t) {
     McRef r;
     r.src_x = t.src_x; r.src_y = t.src_y;

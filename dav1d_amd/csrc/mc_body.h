@@ -43,7 +43,7 @@ __device__ __forceinline__ Taps load_taps(const int set, const int m) {
 constexpr int mc_cmin(int a, int b) { return a < b ? a : b; }
 // window row stride in pixels: TW + 8 columns rounded up to whole 16-byte chunks.  4-wide tiles: blocks of width 4 are only ever
 // filtered with the 4-tap sets, bilinear or the unit tap (reference src/mc_tmpl.c GET_H_FILTER: w > 4 ? type : 3 + (type & 1);
-// the host builds the tiles by the same rule, capi.hip), whose taps 0, 1, 6 and 7 are zero: the 4 outputs of a row reach the 7
+// the host builds the tiles by the same rule, api_lists.hip), whose taps 0, 1, 6 and 7 are zero: the 4 outputs of a row reach the 7
 // columns src_x - 1 .. src_x + 5, so the window starts at src_x - 2 and is one 16-byte piece per row
 constexpr int mc_win_stride(int tw) { return tw == 4 ? 8 : (tw + 8 + 7) & ~7; }
 // The same for a reference stored as 8x8 tiles (TILED, see "tiled twin" below): the window is made of whole tile rows — aligned

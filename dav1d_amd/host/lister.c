@@ -139,7 +139,7 @@ static uint64_t arena_alloc(Walk *w, const int which, uint64_t *cursor, const ui
 static int imin(const int a, const int b) { return a < b ? a : b; }
 static int imax(const int a, const int b) { return a > b ? a : b; }
 static int iclip(const int v, const int lo, const int hi) { return v < lo ? lo : v > hi ? hi : v; }
-/* bin of the <= 64x16 tiles a prediction block is cut into (csrc/capi.hip push_tiles): 3 * class(w) + class(h) */
+/* bin of the <= 64x16 tiles a prediction block is cut into (csrc/api_lists.hip push_tiles): 3 * class(w) + class(h) */
 static int tile_bin(const int w_px, const int h_px) {
     const int tw = imin(w_px, 64), th = imin(h_px, 16);
     return (tw <= 4 ? 0 : tw <= 8 ? 1 : tw <= 16 ? 2 : tw <= 32 ? 3 : 4) * 3 + (th <= 4 ? 0 : th <= 8 ? 1 : 2);

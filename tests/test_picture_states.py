@@ -505,7 +505,7 @@ def _ptr(a):
 # (dav1d_hip_intra_list_run_batch and _run_all go through dav1d_hip_intra_list_run_batch_blend, which holds their check.  Not in the table, and
 # not guarded: dav1d_hip_itx_list_run_timed, dav1d_hip_mc_list_run_timed and dav1d_hip_inter_list_run_timed.  bench.py times them on the
 # pictures of its tiled steps and uses nothing of what they write; they take a picture in any state and leave twin_ok alone, as
-# dav1d_amd/csrc/capi.hip says.  dav1d_hip_recon_list_run_timed IS guarded, like the run it times.)
+# dav1d_amd/csrc/api_lists.hip says (tests/test_timed_runs.py runs them).  dav1d_hip_recon_list_run_timed IS guarded, like the run it times.)
 WRITERS = {
     "lf_batch": lambda l, h, d, s: l.dav1d_hip_lf_batch(h, d, _ptr(s.lf), len(s.lf), s.lvl.ptr, s.post.b4_stride, _ptr(s.lut_e), _ptr(s.lut_i)),
     "ipred_batch": lambda l, h, d, s: l.dav1d_hip_ipred_batch(h, d, _ptr(s.first_wave), len(s.first_wave), None),

@@ -8,7 +8,7 @@ set -e
 cd "$(dirname "$0")/.."
 if [ "$1" = build ]; then
     shift
-    for spec in "$@"; do python tools/build_variant.py "ko_${spec%%=*}" "-DDV_LEAN ${spec#*=}" recon.hip mc.hip itx.hip capi.hip & done
+    for spec in "$@"; do python tools/build_variant.py "ko_${spec%%=*}" "-DDV_LEAN ${spec#*=}" recon.hip mc.hip itx.hip capi.hip api_lists.hip api_recon.hip & done
     wait
 else
     sets="$2"
