@@ -32,6 +32,10 @@ class SurfaceRect(C.Structure):        # == Dav1dHipSurfaceRect
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
 
 
+class RgbParams(C.Structure):         # == Dav1dHipRgbParams
+    _fields_ = [("chroma_pos", C.c_int), ("normalize", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
 class HostPicture(C.Structure):
     _fields_ = [("data", C.c_void_p * 3), ("stride", C.c_ssize_t * 2), ("dev", Picture), ("alloc", C.c_void_p), ("alloc_size", C.c_size_t)]
 
@@ -90,6 +94,7 @@ SYMBOLS = [
     "dav1d_hip_lister_steps", "dav1d_hip_lister_const_masks", "dav1d_hip_lister_destroy",
     "dav1d_hip_lister_mask_offset", "dav1d_hip_lister_tables", "dav1d_hip_lister_block_warp", "dav1d_hip_lister_filter_sbrow",
     "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain", "dav1d_hip_surface_export_scaled", "dav1d_hip_surface_scaled_rows_needed",
+    "dav1d_hip_surface_export_rgb", "dav1d_hip_surface_rgb_rows_needed",
 ]
 
 
@@ -292,6 +297,8 @@ def load(path=None):
         "dav1d_hip_surface_export_grain": (i, [vp, P(Surface), P(Picture), vp, i, i, i]),
         "dav1d_hip_surface_export_scaled": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), i, i]),
         "dav1d_hip_surface_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), i]),
+        "dav1d_hip_surface_export_rgb": (i, [vp, P(Surface), P(Picture), P(RgbParams), i, i]),
+        "dav1d_hip_surface_rgb_rows_needed": (i, [P(Surface), P(Picture), P(RgbParams), i]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

@@ -11,11 +11,12 @@ from . import _lib
 from ._lib import FilmGrainData  # noqa: F401
 from ._lib import ITX_TASK, MC_TASK, COMP_TASK, CDEF_TASK, LF_TASK, IPRED_TASK, LR_TASK, WARP_TASK, MC_SCALED_TASK, Picture, HostPicture  # noqa: F401  (re-exported)
 from ._lib import Surface as SurfaceDesc
-from ._lib import SurfaceRect
+from ._lib import SurfaceRect, RgbParams
 
 LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
-SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR = 0, 1, 2      # enum Dav1dHipSurfaceFormat
-SAMPLE_NATIVE, SAMPLE_MSB16, SAMPLE_F32 = 0, 1, 2                     # enum Dav1dHipSurfaceSample
+SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR, SURFACE_RGB_PACKED, SURFACE_RGBA_PACKED = 0, 1, 2, 3, 4      # enum Dav1dHipSurfaceFormat
+SAMPLE_NATIVE, SAMPLE_MSB16, SAMPLE_F32, SAMPLE_F16 = 0, 1, 2, 3      # enum Dav1dHipSurfaceSample
+CHROMA_REPLICATE, CHROMA_VERTICAL, CHROMA_COLOCATED = 0, 1, 2         # Dav1dHipRgbParams.chroma_pos
 
 
 class HipError(RuntimeError):
@@ -144,6 +145,30 @@ class DevicePicture:
         _chk(min(n, 0), "surface_scaled_rows_needed")
         return n
 
+    @staticmethod
+    def _rgb_params(chroma_pos, scale, bias):
+        if scale is None and bias is None:
+            return RgbParams(int(chroma_pos), 0)
+        p = RgbParams(int(chroma_pos), 1)
+        for k in range(3):
+            p.scale[k] = 1.0 if scale is None else scale[k]
+            p.bias[k] = 0.0 if bias is None else bias[k]
+        return p
+
+    def export_rgb(self, surface, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30):
+        """dav1d_hip_surface_export_rgb: luma rows [row0, row1) as RGB into a planar or packed (RGB / RGBA) surface, any sample type, chroma
+        upsampled at its site (chroma_pos: CHROMA_REPLICATE, CHROMA_VERTICAL, CHROMA_COLOCATED).  `scale` / `bias` (three floats each, R, G, B;
+        float samples only) normalise: out = v * scale[c] + bias[c].  Asynchronous like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), C.byref(p), row0, row1), "surface_export_rgb")
+
+    def rgb_rows_needed(self, surface, chroma_pos, row1):
+        """dav1d_hip_surface_rgb_rows_needed: the luma rows, from the top, that rows [0, row1) of export_rgb read"""
+        p = self._rgb_params(chroma_pos, None, None)
+        n = self.ctx.lib.dav1d_hip_surface_rgb_rows_needed(C.byref(surface.desc), C.byref(self.pic), C.byref(p), row1)
+        _chk(min(n, 0), "surface_rgb_rows_needed")
+        return n
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -161,9 +186,11 @@ class DevicePicture:
 
 def surface_planes(w, h, layout, bpc, fmt, sample):
     """[(rows, samples per row)] of the planes of a surface, and the numpy dtype of its samples (include/dav1d_hip.h, Dav1dHipSurface)."""
-    dt = np.dtype(np.float32 if sample == SAMPLE_F32 else np.uint16 if sample == SAMPLE_MSB16 or bpc > 8 else np.uint8)
+    dt = np.dtype(np.float32 if sample == SAMPLE_F32 else np.float16 if sample == SAMPLE_F16 else np.uint16 if sample == SAMPLE_MSB16 or bpc > 8 else np.uint8)
     if fmt == SURFACE_RGB_PLANAR:
         return [(h, w)] * 3, dt
+    if fmt in (SURFACE_RGB_PACKED, SURFACE_RGBA_PACKED):
+        return [(h, (3 if fmt == SURFACE_RGB_PACKED else 4) * w)], dt
     if layout == LAYOUT_I400:
         return [(h, w)], dt
     cw = (w + 1) >> 1 if layout != LAYOUT_I444 else w
@@ -225,13 +252,16 @@ class Surface:
         self.bufs = None
 
 
-def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0, crop=None, resize=False):
+def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0, crop=None, resize=False,
+                     chroma_pos=None, scale=None, bias=None):
     """Fills torch tensors on the picture's device through tensor.data_ptr(): `tensor` of shape (3, h, w) gets R, G, B planes; with
     `chroma` of shape (ceil(h / 2), 2 * ceil(w / 2)) given, `tensor` (h, w) gets luma and `chroma` the interleaved U, V of a 4:2:0
     picture (NV12 / P010 family).  The sample type follows the dtype (float32: F32; else `sample`, native by default).  The context should
     have been opened on the stream the tensors are used on (api.Context(stream=torch.cuda.current_stream().cuda_stream)).  `grain` / `is_id`:
     as in DevicePicture.export.  `resize=True`: the tensors' shape gives the output size, and `crop` = (x0, y0, w, h) (None: the whole picture)
-    the rectangle that is scaled to it (DevicePicture.export_scaled; rows are then destination rows, and there is no grain)."""
+    the rectangle that is scaled to it (DevicePicture.export_scaled; rows are then destination rows, and there is no grain).
+    A tensor of shape (h, w, 3) or (h, w, 4) gets packed RGB / RGBA, and torch.float16 gets binary16 samples: both go through
+    DevicePicture.export_rgb, as does any RGB tensor when `chroma_pos`, `scale` or `bias` is given (see there; neither grain nor resize then)."""
     import torch
     if crop is not None and not resize:
         raise ValueError("crop= needs resize=True")
@@ -243,11 +273,21 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
         if not t.is_cuda or t.stride(-1) != 1:
             raise ValueError("export_to_tensor needs device tensors with unit stride along a row")
     if sample is None:
-        sample = SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_NATIVE
+        sample = SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_F16 if tensor.dtype == torch.float16 else SAMPLE_NATIVE
     es = tensor.element_size()
-    if chroma is None:
+    packed = chroma is None and tensor.dim() == 3 and tuple(tensor.shape[:2]) == (h, w) and int(tensor.shape[2]) in (3, 4)
+    rgbx = packed or sample == SAMPLE_F16 or chroma_pos is not None or scale is not None or bias is not None
+    if rgbx and (chroma is not None or resize or grain is not None):
+        raise ValueError("packed RGB, float16, chroma_pos, scale and bias go through export_rgb: RGB tensors only, no grain, no resize")
+    if packed:
+        if tensor.stride(1) != int(tensor.shape[2]):
+            raise ValueError("a packed RGB tensor has its channels next to each other")
+        fmt = SURFACE_RGB_PACKED if int(tensor.shape[2]) == 3 else SURFACE_RGBA_PACKED
+        ptrs = [tensor.data_ptr()]
+        strides = [tensor.stride(0) * es]
+    elif chroma is None:
         if tuple(tensor.shape) != (3, h, w):
-            raise ValueError("an RGB tensor has shape (3, h, w)")
+            raise ValueError("an RGB tensor has shape (3, h, w), (h, w, 3) or (h, w, 4)")
         fmt = SURFACE_RGB_PLANAR
         ptrs = [tensor[k].data_ptr() for k in range(3)]
         strides = [tensor.stride(1) * es] * 3
@@ -258,8 +298,11 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
         ptrs = [tensor.data_ptr(), chroma.data_ptr()]
         strides = [tensor.stride(0) * es, chroma.stride(0) * es]
     s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
-    if s.dtype.itemsize != es or [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]:
+    if s.dtype.itemsize != es or (not packed and [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]):
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
+    if rgbx:
+        pic.export_rgb(s, chroma_pos or 0, scale, bias, row0, row1)
+        return s
     if resize:
         pic.export_scaled(s, crop, row0, row1)
         return s

@@ -89,6 +89,40 @@ __device__ __forceinline__ uint32_t pk_lshr(uint32_t v, uint32_t sh2) { return D
 __device__ __forceinline__ uint32_t pk_ashr(uint32_t v, uint32_t sh2) { return DV_R(DV_S2(v) >> DV_S2(sh2)); }
 __device__ __forceinline__ uint32_t pk_mad(uint32_t a, uint32_t b, uint32_t c) { return DV_R(DV_S2(a) * DV_S2(b) + DV_S2(c)); }
 #endif
+// The IEEE binary16 pattern of a float: round to nearest even, subnormals kept, overflow to infinity (what numpy's astype(float16) gives).
+// The device converts in hardware (v_cvt_f16_f32); the emulated build's host compiler has no _Float16 in C++ and gets the integer form.
+__device__ __forceinline__ uint16_t f32_to_f16_bits(const float f) {
+#ifdef DAV1D_HIP_EMU
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x > 0x7f800000u) {                                      // NaN: the top of the payload, never the pattern of infinity
+        const uint32_t m = 0x7c00u + ((x & 0x7fffffu) >> 13);
+        return (uint16_t) (sign | (m == 0x7c00u ? 0x7c01u : m));
+    }
+    if (x >= 0x477ff000u) return (uint16_t) (sign | 0x7c00u);   // 65520 (the tie above the largest finite value) and up, infinity
+    if (x <= 0x33000000u) return (uint16_t) sign;               // 2^-25 (the tie below the smallest subnormal) and down
+    uint32_t m, shift;
+    if (x >= 0x38800000u) { m = x - 0x38000000u; shift = 13; }  // normal: exponent rebiased, a carry out of the mantissa goes where it belongs
+    else { m = (x & 0x7fffffu) | 0x800000u; shift = 126 - (x >> 23); }      // subnormal: in units of 2^-24
+    const uint32_t r = m >> shift, rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
+    return (uint16_t) (sign | (r + (rem > half || (rem == half && (r & 1)))));
+#else
+    return __builtin_bit_cast(uint16_t, (_Float16) f);
+#endif
+}
+// v * s + b with a rounding after the product and one after the sum, never contracted into a fused multiply-add
+__device__ __forceinline__ float mul_add_2r(const float v, const float s, const float b) {
+#ifdef DAV1D_HIP_EMU
+    volatile float p = v * s;
+    return p + b;
+#else
+#pragma clang fp contract(off)
+    const float p = v * s;
+    return p + b;
+#endif
+}
 // clamp with lo <= hi as one instruction (v_med3_i32); the compiler only forms it when both bounds are literals, and the
 // select form of iclip() above costs three
 __device__ __forceinline__ int clamp3(int v, int lo, int hi) {

@@ -161,13 +161,15 @@ struct SurfaceCall {
 };
 
 // (`scaled`: the surface has a size of its own, dav1d_hip_surface_export_scaled — the size rule falls away, its planes and rows are the surface's)
-inline int surface_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, int row0, int row1, SurfaceCall *const call, const bool scaled)
+// (`ext`: dav1d_hip_surface_export_rgb — the packed formats, one plane of 3 or 4 samples a pixel, and binary16 samples are known as well)
+inline int surface_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, int row0, int row1, SurfaceCall *const call, const bool scaled,
+                              const bool ext = false)
 {
     if (!dst || !src || !src->p[0].data) return -EINVAL;
     if (src->bpc != 8 && src->bpc != 10 && src->bpc != 12) return -EINVAL;
     if (src->layout < DAV1D_HIP_LAYOUT_I400 || src->layout > DAV1D_HIP_LAYOUT_I444) return -EINVAL;
-    if (dst->format < DAV1D_HIP_SURFACE_PLANAR || dst->format > DAV1D_HIP_SURFACE_RGB_PLANAR) return -EINVAL;
-    if (dst->sample < DAV1D_HIP_SAMPLE_NATIVE || dst->sample > DAV1D_HIP_SAMPLE_F32) return -EINVAL;
+    if (dst->format < DAV1D_HIP_SURFACE_PLANAR || dst->format > (ext ? DAV1D_HIP_SURFACE_RGBA_PACKED : DAV1D_HIP_SURFACE_RGB_PLANAR)) return -EINVAL;
+    if (dst->sample < DAV1D_HIP_SAMPLE_NATIVE || dst->sample > (ext ? DAV1D_HIP_SAMPLE_F16 : DAV1D_HIP_SAMPLE_F32)) return -EINVAL;
     if (dst->sample == DAV1D_HIP_SAMPLE_MSB16 && src->bpc == 8) return -EINVAL;
     const int w = src->p[0].w, h = src->p[0].h;
     if (w <= 0 || h <= 0) return -EINVAL;
@@ -175,12 +177,13 @@ inline int surface_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPi
     const int mono = src->layout == DAV1D_HIP_LAYOUT_I400;
     const int ss_hor = !mono && src->layout != DAV1D_HIP_LAYOUT_I444, dw = dst->w, dh = dst->h;
     if (!mono && (!src->p[1].data || !src->p[2].data)) return -EINVAL;
-    const ptrdiff_t ss = dst->sample == DAV1D_HIP_SAMPLE_F32 ? 4 : dst->sample == DAV1D_HIP_SAMPLE_MSB16 ? 2 : src->bpc > 8 ? 2 : 1;
-    const bool rgb = dst->format == DAV1D_HIP_SURFACE_RGB_PLANAR;
-    const int n_dst = rgb ? 3 : mono ? 1 : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 : 3;
+    const ptrdiff_t ss = dst->sample == DAV1D_HIP_SAMPLE_F32 ? 4 : dst->sample == DAV1D_HIP_SAMPLE_MSB16 || dst->sample == DAV1D_HIP_SAMPLE_F16 ? 2 : src->bpc > 8 ? 2 : 1;
+    const bool rgb = dst->format >= DAV1D_HIP_SURFACE_RGB_PLANAR;
+    const int packed = dst->format == DAV1D_HIP_SURFACE_RGB_PACKED ? 3 : dst->format == DAV1D_HIP_SURFACE_RGBA_PACKED ? 4 : 0;
+    const int n_dst = packed ? 1 : rgb ? 3 : mono ? 1 : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 : 3;
     for (int k = 0; k < n_dst; k++) {
         const int cw = scaled ? (dw + ss_hor) >> ss_hor : src->p[k].w;
-        const ptrdiff_t row_bytes = ss * (rgb || !k ? dw : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 * cw : cw);
+        const ptrdiff_t row_bytes = ss * (packed ? (ptrdiff_t) packed * dw : rgb || !k ? dw : dst->format == DAV1D_HIP_SURFACE_SEMIPLANAR ? 2 * cw : cw);
         if (!dst->data[k] || dst->stride[k] < row_bytes || dst->stride[k] % ss) return -EINVAL;
     }
     if (rgb) {

@@ -69,6 +69,8 @@ typedef struct Hip {
     int (*surface_export_grain)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipGrain *, int, int, int);
     int (*fg_prepare)(Dav1dHipContext *, Dav1dHipGrain **, const Dav1dHipFilmGrainData *, int, int);
     void (*fg_grain_destroy)(Dav1dHipContext *, Dav1dHipGrain *);
+    int (*fg_apply_prepared)(Dav1dHipContext *, const Dav1dHipPicture *, const Dav1dHipPicture *, const Dav1dHipGrain *, int);
+    int (*surface_export_rgb)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipRgbParams *, int, int);
     int (*frame_set_progress_callback)(Dav1dHipFrame *, void (*)(void *, int, const Dav1dHipPicture *), void *);
     int (*live_objects)(long long *);
     int (*device_count)(void);
@@ -711,6 +713,44 @@ int dav1d_hip_glue_output_surface(Dav1dHipGlue *const g, const Dav1dPicture *con
     return !rc ? 0 : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
 }
 
+/* Tensor-ready RGB (dav1d_hip_surface_export_rgb: sited chroma, packed RGB(A), half floats, normalisation).  Without `params` the chroma site is the
+ * sequence header's (DAV1D_CHR_UNKNOWN counts as vertical, the common case), nothing is normalised.  With grain this is the two-pass route, stated as
+ * such: the export with grain fused in replicates chroma, so the grain goes into a temporary picture first (dav1d_hip_fg_prepare,
+ * dav1d_hip_fg_apply_prepared) and the RGB export reads that; dav1d_hip_sync, then the temporary and the handle go away.  Tested at the C ABI like
+ * the function above (tests/test_surface_rgb.py mirrors the call sequence). */
+int dav1d_hip_glue_output_rgb(Dav1dHipGlue *const g, const Dav1dPicture *const pic, const Dav1dHipSurface *const dst, const Dav1dHipRgbParams *const params,
+                              const int apply_grain) {
+    if (!g || !pic || !pic->allocator_data || !dst) return DAV1D_ERR(EINVAL);
+    const Dav1dHipGluePicture *const hp = pic->allocator_data;
+    const Dav1dFilmGrainData *const fg = &pic->frame_hdr->film_grain.data;
+    const int grain_here = apply_grain && (fg->num_y_points || fg->num_uv_points[0] || fg->num_uv_points[1] ||
+                                           (fg->clip_to_restricted_range && fg->chroma_scaling_from_luma));
+    Dav1dHipRgbParams p;
+    memset(&p, 0, sizeof(p));
+    if (params) p = *params;
+    else p.chroma_pos = pic->seq_hdr->chr == DAV1D_CHR_COLOCATED ? 2 : 1;
+    Dav1dHipGrain *grain = NULL;
+    Dav1dHipPicture tmp;
+    memset(&tmp, 0, sizeof(tmp));
+    Dav1dHipContext *const ctx_out = g->dev[hp->ref_dev].ctx_out;
+    const int thread_dev = borrow_thread(g, ctx_out);
+    int rc = 0, no_mem = 0;
+    if (grain_here) {
+        rc = g->hip.fg_prepare(ctx_out, &grain, (const Dav1dHipFilmGrainData *) fg, pic->p.bpc, pic->p.layout);
+        if (!rc) rc = g->hip.picture_alloc(ctx_out, &tmp, pic->p.w, pic->p.h, pic->p.layout, pic->p.bpc);
+        no_mem = rc == -ENOMEM;
+        if (!rc) rc = g->hip.fg_apply_prepared(ctx_out, &tmp, &hp->ref, grain, pic->seq_hdr->mtrx == DAV1D_MC_IDENTITY);
+        if (!rc) rc = g->hip.surface_export_rgb(ctx_out, dst, &tmp, &p, 0, pic->p.h);
+    } else
+        rc = g->hip.surface_export_rgb(ctx_out, dst, &hp->ref, &p, 0, pic->p.h);
+    const int bad_args = rc == -EINVAL || rc == -ENOTSUP;
+    if (!rc) rc = g->hip.sync(ctx_out);
+    if (tmp.alloc) g->hip.picture_free(ctx_out, &tmp);
+    if (grain) g->hip.fg_grain_destroy(ctx_out, grain);
+    return_thread(g, thread_dev);
+    return !rc ? 0 : no_mem ? DAV1D_ERR(ENOMEM) : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
+}
+
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *const g) { return g ? atomic_load(&g->n_backend_failures) : 0; }
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *const g) { return g ? atomic_load(&g->n_row_publications) : 0; }
 int dav1d_hip_glue_devices(const Dav1dHipGlue *const g) { return g ? g->n_dev : 0; }
@@ -749,7 +789,8 @@ int dav1d_hip_glue_create(Dav1dHipGlue **const out, const Dav1dHipGlueOptions *c
     SYM(frame_submit_intra_step, "dav1d_hip_frame_submit_intra_step"); SYM(frame_set_super_res, "dav1d_hip_frame_set_super_res");
     SYM(fg_apply, "dav1d_hip_fg_apply"); SYM(picture_alloc, "dav1d_hip_picture_alloc"); SYM(picture_free, "dav1d_hip_picture_free");
     SYM(plane_download, "dav1d_hip_plane_download"); SYM(surface_export, "dav1d_hip_surface_export"); SYM(surface_export_grain, "dav1d_hip_surface_export_grain");
-    SYM(fg_prepare, "dav1d_hip_fg_prepare"); SYM(fg_grain_destroy, "dav1d_hip_fg_grain_destroy"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
+    SYM(fg_prepare, "dav1d_hip_fg_prepare"); SYM(fg_grain_destroy, "dav1d_hip_fg_grain_destroy"); SYM(fg_apply_prepared, "dav1d_hip_fg_apply_prepared");
+    SYM(surface_export_rgb, "dav1d_hip_surface_export_rgb"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
     SYM(live_objects, "dav1d_hip_live_objects"); SYM(device_count, "dav1d_hip_device_count"); SYM(use, "dav1d_hip_context_use");
     SYM(enable_peer_access, "dav1d_hip_enable_peer_access"); SYM(current_device, "dav1d_hip_current_device"); SYM(set_device, "dav1d_hip_set_device");
     SYM(picture_copy_peer, "dav1d_hip_picture_copy_peer"); SYM(picture_copy_peer_rows, "dav1d_hip_picture_copy_peer_rows"); SYM(picture_retile, "dav1d_hip_picture_retile");

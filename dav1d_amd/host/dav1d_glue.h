@@ -102,6 +102,10 @@ int dav1d_hip_glue_output_with_grain(Dav1dHipGlue *g, const Dav1dPicture *pic, u
  * memory on the device the picture's pixels live on), with its film grain when apply_grain is set and the frame header carries any.  dst->matrix and
  * dst->full_range are the caller's; pic->seq_hdr->mtrx and pic->seq_hdr->color_range are the usual source.  Returns when the surface is written. */
 int dav1d_hip_glue_output_surface(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, int apply_grain);
+/* ---- the same as tensor-ready RGB (dav1d_hip_surface_export_rgb: planar or packed RGB(A), any sample type, chroma upsampled at its site).  `params`
+ * NULL: chroma_pos from pic->seq_hdr->chr (DAV1D_CHR_COLOCATED: 2, DAV1D_CHR_VERTICAL and DAV1D_CHR_UNKNOWN: 1), no normalisation.  With grain: two
+ * passes, the grain into a temporary picture and the export from that.  Returns when the surface is written. */
+int dav1d_hip_glue_output_rgb(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, const Dav1dHipRgbParams *params, int apply_grain);
 
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *g);    /* frames that failed INSIDE the backend (not: frames dav1d rejects) */
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *g);

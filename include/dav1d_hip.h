@@ -235,11 +235,14 @@ enum Dav1dHipSurfaceFormat {
     DAV1D_HIP_SURFACE_PLANAR     = 0,  /* data[0..2] = Y, U, V (I400: Y only) */
     DAV1D_HIP_SURFACE_SEMIPLANAR = 1,  /* data[0] = Y, data[1] = U,V interleaved (NV12 / P010 family; I400: Y only) */
     DAV1D_HIP_SURFACE_RGB_PLANAR = 2,  /* data[0..2] = R, G, B, each at luma size */
+    DAV1D_HIP_SURFACE_RGB_PACKED = 3,  /* data[0]: R,G,B interleaved, 3 samples a pixel (dav1d_hip_surface_export_rgb only) */
+    DAV1D_HIP_SURFACE_RGBA_PACKED = 4, /* data[0]: R,G,B,A interleaved, A = opaque (dav1d_hip_surface_export_rgb only) */
 };
 enum Dav1dHipSurfaceSample {
     DAV1D_HIP_SAMPLE_NATIVE = 0,       /* uint8 at 8 bpc, uint16 with the value in the LOW bits at 10 / 12 bpc */
     DAV1D_HIP_SAMPLE_MSB16  = 1,       /* uint16, value << (16 - bpc): P010 / P012 / P210 / P410; 8 bpc: -EINVAL */
     DAV1D_HIP_SAMPLE_F32    = 2,       /* float, (float) value * (1.0f / ((1 << bpc) - 1)): one float multiply */
+    DAV1D_HIP_SAMPLE_F16    = 3,       /* IEEE binary16 of the float32 value, round to nearest even (dav1d_hip_surface_export_rgb only) */
 };
 typedef struct Dav1dHipSurface {
     void *data[3];        /* DEVICE memory of the caller (dav1d_hip_malloc, a torch tensor, ...) on the context's device */
@@ -292,6 +295,34 @@ typedef struct Dav1dHipSurfaceRect { int x0, y0, w, h; } Dav1dHipSurfaceRect;
 DAV1D_HIP_API int dav1d_hip_surface_export_scaled(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
                                                   const Dav1dHipSurfaceRect *crop, int drow0, int drow1);
 DAV1D_HIP_API int dav1d_hip_surface_scaled_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop, int drow1);
+/* Tensor-ready RGB (dav1d_amd/csrc/surface_rgb.hip): the RGB export with sited chroma, packed layouts, half floats and a
+ * normalisation.  dst->format is RGB_PLANAR, RGB_PACKED or RGBA_PACKED (a packed row is 3 w or 4 w samples; only data[0] / stride[0] are read),
+ * dst->sample any of the four.  The three calls above keep refusing formats 3, 4 and sample 3.
+ * Chroma (params->chroma_pos; 0 = replicate, the rule above; 1 = AV1 CSP_VERTICAL; 2 = AV1 CSP_COLOCATED) is upsampled in integers.  C is a chroma
+ * plane of cw x ch samples, cl(i, n) = min(max(i, 0), n - 1).  Horizontal taps (chroma column, weight), sum 2: ss_hor == 0: {(x, 2)}; x = 2k: {(k, 2)};
+ * x = 2k + 1: {(k, 1), (k + 1, 1)} (both positions are co-sited with even luma columns).  Vertical taps (chroma row, weight), sum 4: ss_ver == 0:
+ * {(y, 4)}; chroma_pos 1 (chroma midway between luma rows 2k and 2k + 1): y = 2k: {(k - 1, 1), (k, 3)}, y = 2k + 1: {(k, 3), (k + 1, 1)}; chroma_pos 2:
+ * y = 2k: {(k, 4)}, y = 2k + 1: {(k, 2), (k + 1, 2)}.  up(x, y) = (sum over both tap sets of wh wv C[cl(row, ch)][cl(col, cw)] + 4) >> 3: one
+ * rounding, within [0, max].  U' = up(U), V' = up(V) take the place of the replicated samples in the RGB formula.  chroma_pos 0, 4:4:4 and 4:0:0 give
+ * exactly the values of dav1d_hip_surface_export.
+ * Samples: NATIVE and MSB16 as above.  Floats: f = (float) v * (1.0f / max) without normalisation, else f = (float) v * scale[c] + bias[c], c = R, G,
+ * B, with a rounding after the product and another after the sum (never fused).  F32 stores f, F16 the binary16 nearest to f (ties to even, subnormals
+ * kept, overflow to infinity).  Alpha is max (NATIVE), max << (16 - bpc) (MSB16), 1.0 (floats, whatever the normalisation).
+ * Rows [row0, row1) as above; a band writes the bytes a whole-picture call writes for those rows and therefore reads up to one chroma row above and one
+ * below its own: dav1d_hip_surface_rgb_rows_needed (host arithmetic) is the number of luma rows from the top that must be final for rows [0, row1):
+ * min(h, row1 + 2) when ss_ver == 1 and chroma_pos != 0, else min(h, row1) (0 for row1 <= 0), or a negative errno for what the export would refuse.
+ * Asynchronous exactly like dav1d_hip_surface_export: one launch on the context's stream, dav1d_hip_last_kernel_ms reports its device time, `src` is
+ * const and a DAV1D_HIP_TWIN_ONLY picture stays one, no allocation, no host wait, nothing written outside the visible samples of the rows asked for.
+ * Errors, before anything is enqueued: everything dav1d_hip_surface_export refuses, with its code (a packed format needs data[0] and a stride[0] of
+ * at least 3 w / 4 w samples only); -EINVAL for a format below RGB_PLANAR, chroma_pos outside 0..2, normalize != 0 with an integer sample. */
+typedef struct Dav1dHipRgbParams {
+    int chroma_pos;          /* 0: replicate; 1: AV1 CSP_VERTICAL (and CSP_UNKNOWN); 2: AV1 CSP_COLOCATED */
+    int normalize;           /* float samples only: out = v * scale[c] + bias[c], c = R, G, B */
+    float scale[3], bias[3];
+} Dav1dHipRgbParams;
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                               const Dav1dHipRgbParams *params /* NULL = all zero */, int row0, int row1);
+DAV1D_HIP_API int dav1d_hip_surface_rgb_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipRgbParams *params, int row1);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

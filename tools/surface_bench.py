@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -14,6 +14,9 @@ into a pre-allocated picture, then dav1d_hip_surface_export from that, on source
 --scaled: dav1d_hip_surface_export_scaled at 2:1 (8K to 4K) and 4:1 (8K to 1080p) as planar native, P010 and RGB planar native, against the
 yardstick a user pays today before any scaler of their own runs: dav1d_hip_surface_export of the same picture at full size in the same format,
 timed the same way in the same run.
+--rgb: dav1d_hip_surface_export_rgb (sited chroma, packed RGB / RGBA, binary16) against dav1d_hip_surface_export to RGB planes of the same sample
+type in the same run (binary16: the float32 export); where a variant writes more bytes than its yardstick (RGBA: 4/3 of the writes) the
+yardstick's times are scaled by the bytes moved.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -182,11 +185,77 @@ def scaled_runs(a, ctx, ev, pics, variants, src_bytes):
     ctx.close()
 
 
+def rgb_runs(a, ctx, ev, pics, src_bytes):
+    """the RGB export's variants against the plain export to RGB planes of the same sample type (binary16: of float32)"""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    R, K3, K4 = api.SURFACE_RGB_PLANAR, api.SURFACE_RGB_PACKED, api.SURFACE_RGBA_PACKED
+    N, F32, F16 = api.SAMPLE_NATIVE, api.SAMPLE_F32, api.SAMPLE_F16
+    runs, all_surfs = [], []
+
+    def add(name, fmt, sample, es, pos, yard, plain=False):
+        n = 4 if fmt == K4 else 3
+        surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
+        all_surfs.extend(surfs)
+        if plain:
+            def call(k):
+                pics[k % a.pairs].export(surfs[k % a.pairs])
+        else:
+            def call(k):
+                pics[k % a.pairs].export_rgb(surfs[k % a.pairs], pos)
+        runs.append((name, src_bytes + n * es * w * h, call, yard))
+        return name
+    y_n = add("export: RGB planar native (yardstick)", R, N, 2, 0, None, plain=True)
+    add("export_rgb: planar native, chroma_pos 0", R, N, 2, 0, y_n)
+    add("export_rgb: planar native, chroma_pos 1", R, N, 2, 1, y_n)
+    add("export_rgb: planar native, chroma_pos 2", R, N, 2, 2, y_n)
+    add("export_rgb: packed RGB native, chroma_pos 1", K3, N, 2, 1, y_n)
+    add("export_rgb: packed RGBA native, chroma_pos 1", K4, N, 2, 1, y_n)
+    y_f = add("export: RGB planar float32 (yardstick)", R, F32, 4, 0, None, plain=True)
+    add("export_rgb: planar float32, chroma_pos 1", R, F32, 4, 1, y_f)
+    add("export_rgb: planar float16, chroma_pos 1", R, F16, 2, 1, y_f)
+    add("export_rgb: packed RGB float16, chroma_pos 1", K3, F16, 2, 1, y_f)
+    add("export_rgb: packed RGBA float16, chroma_pos 1", K4, F16, 2, 1, y_f)
+    print("# surface_bench --rgb on %s: %dx%d 4:2:0 %d-bit twin-only sources, %d picture / surface pairs in rotation, 20 warm-up + %d timed calls per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, a.pairs, a.calls, a.repeats))
+    print("# bytes per call = bytes read + bytes written, from the shapes")
+    results = {r[0]: [] for r in runs}
+    nbytes_of = {r[0]: r[1] for r in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, call, _ in runs:
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            print("repeat %d  %-62s %8.4f ms/call  %7.1f MB/call  %7.0f GB/s" % (rep, name, ms, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (min / median / max ms per call over the repeats)")
+    for name, nbytes, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-62s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    for name, nbytes, _, yard in runs:
+        if yard is None:
+            continue
+        f = max(1.0, nbytes / nbytes_of[yard])          # more bytes than the yardstick moves: its time scaled by the bytes; fewer: its time as it is
+        v, u = sorted(results[name]), sorted(results[yard])
+        ok = v[len(v) // 2] <= f * (u[len(u) // 2] + (u[-1] - u[0]))
+        print("condition %-62s median %.4f ms <= %.3f x (yardstick median %.4f ms + its spread %.4f ms): %s"
+              % (name, v[len(v) // 2], f, u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met"))
+    for s in all_surfs:
+        s.free()
+    for p in pics:
+        p.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
     ap.add_argument("--grain", action="store_true", help="the fused grain + export variants against fg_apply_prepared + export")
     ap.add_argument("--scaled", action="store_true", help="dav1d_hip_surface_export_scaled at 2:1 and 4:1 against the plain export at full size")
+    ap.add_argument("--rgb", action="store_true", help="dav1d_hip_surface_export_rgb (sited chroma, packed, float16) against the plain export to RGB planes")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -220,6 +289,8 @@ def main():
         return grain_runs(a, ctx, ev, pics, variants[:3], src_bytes)
     if a.scaled:
         return scaled_runs(a, ctx, ev, pics, variants[:3], src_bytes)
+    if a.rgb:
+        return rgb_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
