@@ -95,6 +95,7 @@ SYMBOLS = [
     "dav1d_hip_lister_mask_offset", "dav1d_hip_lister_tables", "dav1d_hip_lister_block_warp", "dav1d_hip_lister_filter_sbrow",
     "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain", "dav1d_hip_surface_export_scaled", "dav1d_hip_surface_scaled_rows_needed",
     "dav1d_hip_surface_export_rgb", "dav1d_hip_surface_rgb_rows_needed",
+    "dav1d_hip_surface_export_rgb_scaled", "dav1d_hip_surface_rgb_scaled_rows_needed",
 ]
 
 
@@ -299,6 +300,8 @@ def load(path=None):
         "dav1d_hip_surface_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), i]),
         "dav1d_hip_surface_export_rgb": (i, [vp, P(Surface), P(Picture), P(RgbParams), i, i]),
         "dav1d_hip_surface_rgb_rows_needed": (i, [P(Surface), P(Picture), P(RgbParams), i]),
+        "dav1d_hip_surface_export_rgb_scaled": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
+        "dav1d_hip_surface_rgb_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

@@ -169,6 +169,21 @@ class DevicePicture:
         _chk(min(n, 0), "surface_rgb_rows_needed")
         return n
 
+    def export_rgb_scaled(self, surface, crop=None, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30):
+        """dav1d_hip_surface_export_rgb_scaled: export_scaled and export_rgb in one pass — the rectangle `crop` (None: all of the picture) scaled
+        down to the surface's size, as RGB planes or packed RGB / RGBA of any sample type, the scaled chroma upsampled at `chroma_pos`, normalised
+        by `scale` / `bias`; DESTINATION luma rows [row0, row1).  Asynchronous like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_scaled(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), row0, row1),
+             "surface_export_rgb_scaled")
+
+    def rgb_scaled_rows_needed(self, surface, crop, chroma_pos, row1):
+        """dav1d_hip_surface_rgb_scaled_rows_needed: the source luma rows, from the top, that destination rows [0, row1) of export_rgb_scaled read"""
+        p = self._rgb_params(chroma_pos, None, None)
+        n = self.ctx.lib.dav1d_hip_surface_rgb_scaled_rows_needed(C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), row1)
+        _chk(min(n, 0), "surface_rgb_scaled_rows_needed")
+        return n
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -261,13 +276,19 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     as in DevicePicture.export.  `resize=True`: the tensors' shape gives the output size, and `crop` = (x0, y0, w, h) (None: the whole picture)
     the rectangle that is scaled to it (DevicePicture.export_scaled; rows are then destination rows, and there is no grain).
     A tensor of shape (h, w, 3) or (h, w, 4) gets packed RGB / RGBA, and torch.float16 gets binary16 samples: both go through
-    DevicePicture.export_rgb, as does any RGB tensor when `chroma_pos`, `scale` or `bias` is given (see there; neither grain nor resize then)."""
+    DevicePicture.export_rgb, as does any RGB tensor when `chroma_pos`, `scale` or `bias` is given (see there; no grain then).  With `resize=True`
+    these go through DevicePicture.export_rgb_scaled; the output size of a packed tensor is its shape[0] x shape[1] (a shape that reads both ways, (3, n, 3) or (3, n, 4), raises ValueError with these options)."""
     import torch
     if crop is not None and not resize:
         raise ValueError("crop= needs resize=True")
     if resize and grain is not None:
         raise ValueError("the scaled export applies no film grain")
-    w, h = (int(tensor.shape[-1]), int(tensor.shape[-2])) if resize else (pic.w, pic.h)
+    hwc = resize and chroma is None and tensor.dim() == 3 and int(tensor.shape[2]) in (3, 4)
+    if hwc and int(tensor.shape[0]) == 3:          # (3, n, 3) or (3, n, 4): planes of width 3 / 4, or a packed picture of height 3
+        if tensor.dtype == torch.float16 or chroma_pos is not None or scale is not None or bias is not None:
+            raise ValueError("a tensor of shape %s can be read as (3, h, w) and as (h, w, 3 or 4): not accepted with resize=True" % (tuple(tensor.shape),))
+        hwc = False                                # what worked before these options: planes
+    w, h = (int(tensor.shape[1]), int(tensor.shape[0])) if hwc else (int(tensor.shape[-1]), int(tensor.shape[-2])) if resize else (pic.w, pic.h)
     ts = [tensor] if chroma is None else [tensor, chroma]
     for t in ts:
         if not t.is_cuda or t.stride(-1) != 1:
@@ -277,8 +298,8 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     es = tensor.element_size()
     packed = chroma is None and tensor.dim() == 3 and tuple(tensor.shape[:2]) == (h, w) and int(tensor.shape[2]) in (3, 4)
     rgbx = packed or sample == SAMPLE_F16 or chroma_pos is not None or scale is not None or bias is not None
-    if rgbx and (chroma is not None or resize or grain is not None):
-        raise ValueError("packed RGB, float16, chroma_pos, scale and bias go through export_rgb: RGB tensors only, no grain, no resize")
+    if rgbx and (chroma is not None or grain is not None):
+        raise ValueError("packed RGB, float16, chroma_pos, scale and bias go through export_rgb / export_rgb_scaled: RGB tensors only, no grain")
     if packed:
         if tensor.stride(1) != int(tensor.shape[2]):
             raise ValueError("a packed RGB tensor has its channels next to each other")
@@ -300,6 +321,9 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
     if s.dtype.itemsize != es or (not packed and [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]):
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
+    if rgbx and resize:
+        pic.export_rgb_scaled(s, crop, chroma_pos or 0, scale, bias, row0, row1)
+        return s
     if rgbx:
         pic.export_rgb(s, chroma_pos or 0, scale, bias, row0, row1)
         return s

@@ -1,5 +1,5 @@
 // What the output units share (surface.hip: the plain export; surface_grain.hip: the export with film grain fused in; surface_scale.hip: the export
-// with a crop and a scaler in front): the 8-sample unit and
+// with a crop and a scaler in front; surface_rgb.hip: tensor-ready RGB; surface_rgb_scale.hip: that behind the scaler): the 8-sample unit and
 // its loads and stores, the output sample functors, the kernel arguments and how a call is checked and turned into them.  See surface.hip for the
 // layout of a wave (8 rows x 8 units, a 64 x 8 cell of a plane).
 #pragma once
@@ -292,6 +292,232 @@ CopyArgs make_copy_args(const Dav1dHipSurface *const dst, const Dav1dHipPicture 
     }
     for (int k = n_parts; k < 3; k++) { a.part[k] = a.part[0]; a.part[k].n_waves = 0; }
     return a;
+}
+
+// ---- the output samples of the tensor-ready RGB exports (surface_rgb.hip, surface_rgb_scale.hip)
+
+// ---- output samples of channel ch (0, 1, 2 = R, G, B), and the opaque alpha of the sample type
+template <typename Base> struct RgbInt {
+    typedef typename Base::T T;
+    Base b; T alpha;
+    __device__ __forceinline__ T operator()(const int v, const int) const { return b(v); }
+};
+struct RgbF32 {
+    typedef float T;
+    float scale[3], bias[3]; T alpha;
+    __device__ __forceinline__ T operator()(const int v, const int ch) const { return dv::mul_add_2r((float) v, scale[ch], bias[ch]); }
+};
+struct RgbF16 {
+    typedef uint16_t T;
+    float scale[3], bias[3]; T alpha;
+    __device__ __forceinline__ T operator()(const int v, const int ch) const { return dv::f32_to_f16_bits(dv::mul_add_2r((float) v, scale[ch], bias[ch])); }
+};
+
+// N output samples to consecutive addresses, N * sizeof(T) any multiple of 8: vector stores of 16 bytes (8 where the run is no multiple of 16: 24 bytes
+// of uint8 RGB) where the destination allows and the run is whole, else the first n one by one
+template <typename T, int N>
+__device__ __forceinline__ void store_packed(T *const dst, const T (&t)[N], const int n, const bool wide)
+{
+    constexpr int BYTES = N * (int) sizeof(T), CH = BYTES % 16 ? 8 : 16;
+    static_assert(BYTES % CH == 0, "whole chunks");
+    if (wide && n >= N) {
+#pragma unroll
+        for (int i = 0; i < BYTES / CH; i++) {
+            Piece<CH> pc;
+            __builtin_memcpy(&pc, (const char *) t + i * CH, CH);
+            reinterpret_cast<Piece<CH> *>(dst)[i] = pc;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) if (i < n) dst[i] = t[i];
+    }
+}
+
+// what the tensor-ready calls refuse beyond the export's own rules
+inline int rgb_params_check(const Dav1dHipSurface *const dst, const Dav1dHipRgbParams &p)
+{
+    if (dst->format < DAV1D_HIP_SURFACE_RGB_PLANAR) return -EINVAL;
+    if (p.chroma_pos < 0 || p.chroma_pos > 2) return -EINVAL;
+    if (p.normalize && dst->sample != DAV1D_HIP_SAMPLE_F32 && dst->sample != DAV1D_HIP_SAMPLE_F16) return -EINVAL;
+    return 0;
+}
+
+template <typename F> void set_float(F &o, const Dav1dHipRgbParams &p, const int bpc)
+{
+    for (int k = 0; k < 3; k++) {
+        o.scale[k] = p.normalize ? p.scale[k] : (float) (1.0 / (double) ((1 << bpc) - 1));
+        o.bias[k] = p.normalize ? p.bias[k] : 0.0f;          // (x + 0 is x: without normalisation this is OutF32's one multiply)
+    }
+}
+
+// ---- the area scaler S of DESIGN.md 10.2 (surface_scale.hip, surface_rgb_scale.hip): a workgroup of four waves scales a cell of a plane through LDS
+
+constexpr int SC_OW = 128, SC_OR = 8, SC_TAPS = 9;      // the largest cell; taps per axis
+constexpr int SC_MAXU = 33;                             // units of 8 samples across a window: 257 samples from an offset of up to 7
+constexpr int SC_PITCH = SC_MAXU * 8 + 8;               // samples per LDS row
+constexpr int SC_MAXR = 40;                             // rows of a window: 33 from an offset of up to 7
+
+struct ScalePlane {
+    const void *s;
+    int sstride, swide, pw;     // pixels per row; one vector load per unit; visible samples per row of the plane (the narrow loads end there)
+    int x0, y0, sw, sh;         // the window of the plane that is scaled
+    int dw, dh;                 // ... to this size
+    int ow, oh;                 // the cell
+};
+
+template <typename pixel> struct ScaleLds {
+    alignas(16) pixel raw[SC_MAXR * SC_PITCH];
+    uint32_t t[SC_OR * SC_PITCH];
+    uint16_t wx[SC_TAPS][SC_OW], wy[SC_TAPS][SC_OR];
+    uint16_t ix[SC_OW], iy[SC_OR];      // the first tap: column / row of the LDS window
+    uint8_t nx[SC_OW], ny[SC_OR];       // taps
+    union {                                 // the outputs: three planes of samples, or (surface_rgb_scale.hip) luma and a plane of chroma pairs u | v << 16
+        alignas(16) uint16_t out[3][SC_OR * SC_OW];
+        struct { uint16_t y[SC_OR * SC_OW]; uint32_t uv[SC_OR * SC_OW]; } pair;
+    };
+};
+
+// taps and weights of output `o` of an axis (s source samples to d); *first = i0
+__device__ __forceinline__ int scale_weights(const int o, const int s, const int d, int *const first, uint16_t *const w, const int wstride)
+{
+    const uint64_t a = (uint64_t) o * (unsigned) s, b = a + (unsigned) s;
+    const int i0 = (int) (a / (unsigned) d), i1 = (int) ((b + (unsigned) d - 1) / (unsigned) d) - 1;
+    const int n = i1 - i0 + 1;
+    uint64_t edge = (uint64_t) (i0 + 1) * (unsigned) d;
+    unsigned prev = 0;
+    for (int k = 0; k < SC_TAPS; k++, edge += (unsigned) d) {
+        if (k >= n) break;
+        const unsigned cov = (unsigned) ((edge < b ? edge : b) - a);           // <= s
+        const unsigned q = (cov * 4096u + ((unsigned) s >> 1)) / (unsigned) s;
+        w[k * wstride] = (uint16_t) (q - prev);
+        prev = q;
+    }
+    *first = i0;
+    return n;
+}
+
+// Outputs [ox0, ox0 + nox) x [j0, j1) of plane p into out[(j - oyb) * SC_OW + (o - ox0)].  Every argument is uniform in the workgroup; all of
+// its threads call.  nox <= SC_OW, oyb <= j0, j1 - oyb <= SC_OR.  HALF 0: `out` holds samples (uint16_t).  HALF 1 / 2: `out` holds pairs (uint32_t),
+// the call sets the word to the sample / adds the sample as its upper half (U, then V of the same outputs: the same thread owns the word both times).
+template <typename pixel, bool TILED, int HALF = 0, typename O = uint16_t>
+__device__ __forceinline__ void scale_cell(ScaleLds<pixel> &L, const ScalePlane &p, const int ox0, const int nox, const int oyb, const int j0, const int j1,
+                                           O *const out)
+{
+    typedef Piece<8 * sizeof(pixel)> piece_t;
+    if (j1 <= j0 || nox <= 0) return;
+    const int tid = (int) threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int ax0 = p.x0 + (int) ((uint64_t) ox0 * (unsigned) p.sw / (unsigned) p.dw);
+    const int ax1 = p.x0 + (int) (((uint64_t) (ox0 + nox) * (unsigned) p.sw + (unsigned) p.dw - 1) / (unsigned) p.dw);
+    const int ay0 = p.y0 + (int) ((uint64_t) j0 * (unsigned) p.sh / (unsigned) p.dh);
+    const int ay1 = p.y0 + (int) (((uint64_t) j1 * (unsigned) p.sh + (unsigned) p.dh - 1) / (unsigned) p.dh);
+    const int ux0 = ax0 & ~7, ry0 = ay0 & ~7;
+    const int ncols = ax1 - ux0, nrows = ay1 - ry0;
+    const int nU = (ncols + 7) >> 3, nUg = (nU + 7) >> 3, nRg = (nrows + 7) >> 3;
+    if (nU > SC_MAXU || nrows > SC_MAXR) return;          // (not with the cells the host chooses)
+    // ---- the window: a wave takes 8 rows x 8 units at a time, four loads in flight
+    const int n_items = nUg * nRg, r = lane >> 3, c = lane & 7;
+    for (int base = wave; base < n_items; base += 16) {
+        piece_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int it = base + 4 * k, rg = it / nUg, ug = it - rg * nUg;
+            const int unit = ug * 8 + c, y = ry0 + rg * 8 + r, x = ux0 + unit * 8;
+            if (it < n_items && unit < nU && y >= ay0 && y < ay1) v[k] = load8<pixel, TILED>(p.s, p.sstride, x, y, p.pw - x, p.swide);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int it = base + 4 * k, rg = it / nUg, ug = it - rg * nUg;
+            const int unit = ug * 8 + c, y = ry0 + rg * 8 + r;
+            if (it < n_items && unit < nU && y >= ay0 && y < ay1) *reinterpret_cast<piece_t *>(&L.raw[(y - ry0) * SC_PITCH + unit * 8]) = v[k];
+        }
+    }
+    // ---- the weights
+    if (tid < nox) {
+        int i0;
+        L.nx[tid] = (uint8_t) scale_weights(ox0 + tid, p.sw, p.dw, &i0, &L.wx[0][tid], SC_OW);
+        L.ix[tid] = (uint16_t) (p.x0 + i0 - ux0);
+    } else if (tid >= SC_OW && tid < SC_OW + (j1 - j0)) {
+        const int jr = j0 - oyb + tid - SC_OW;
+        int i0;
+        L.ny[jr] = (uint8_t) scale_weights(oyb + jr, p.sh, p.dh, &i0, &L.wy[0][jr], SC_OR);
+        L.iy[jr] = (uint16_t) (p.y0 + i0 - ry0);
+    }
+    __syncthreads();
+    // ---- down: every column of the window, for the rows of the cell
+    const int nj = j1 - j0;
+    for (int it = tid; it < nj * ncols; it += 256) {
+        const int j = it / ncols, col = it - j * ncols, jr = j + j0 - oyb;
+        const pixel *const src = &L.raw[L.iy[jr] * SC_PITCH + col];
+        const int n = L.ny[jr];
+        unsigned sum = 8;
+#pragma unroll
+        for (int k = 0; k < SC_TAPS; k++)
+            if (k < n) sum = dv::mad_u24(L.wy[k][jr], src[k * SC_PITCH], sum);
+        L.t[j * SC_PITCH + col] = sum >> 4;
+    }
+    __syncthreads();
+    // ---- across
+    for (int it = tid; it < nj * nox; it += 256) {
+        const int j = it / nox, o = it - j * nox;
+        const uint32_t *const src = &L.t[j * SC_PITCH + L.ix[o]];
+        const int n = L.nx[o];
+        unsigned sum = 1u << 19;
+#pragma unroll
+        for (int k = 0; k < SC_TAPS; k++)
+            if (k < n) sum = dv::mad_u24(L.wx[k][o], src[k], sum);
+        O &dst = out[(j + j0 - oyb) * SC_OW + o];
+        if (HALF == 2) dst |= (O) (sum >> 20) << 16;
+        else dst = (O) (sum >> 20);
+    }
+    __syncthreads();
+}
+
+struct ScaleGeom {
+    int x0, y0, w, h;       // the crop
+    int dw, dh;
+    int mono, ss_hor, ss_ver;
+};
+
+// the crop and the ratio: what dav1d_hip_surface_export_scaled refuses beyond what the plain export does
+inline int scale_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, ScaleGeom *const g)
+{
+    const int W = src->p[0].w, H = src->p[0].h;
+    g->mono = src->layout == DAV1D_HIP_LAYOUT_I400;
+    g->ss_ver = src->layout == DAV1D_HIP_LAYOUT_I420; g->ss_hor = !g->mono && src->layout != DAV1D_HIP_LAYOUT_I444;
+    g->x0 = crop ? crop->x0 : 0; g->y0 = crop ? crop->y0 : 0; g->w = crop ? crop->w : W; g->h = crop ? crop->h : H;
+    g->dw = dst->w; g->dh = dst->h;
+    if (g->w <= 0 || g->h <= 0 || g->x0 < 0 || g->y0 < 0 || g->x0 > W - g->w || g->y0 > H - g->h) return -EINVAL;
+    if ((g->ss_hor && (g->x0 & 1)) || (g->ss_ver && (g->y0 & 1))) return -EINVAL;
+    if (g->dw > g->w || g->dh > g->h || g->w > 8LL * g->dw || g->h > 8LL * g->dh) return -ENOTSUP;
+    return 0;
+}
+
+template <typename pixel, bool TILED>
+ScalePlane make_scale_plane(const Dav1dHipPicture *const src, void *const *const planes, const ScaleGeom &g, const int pl)
+{
+    const int ssh = pl ? g.ss_hor : 0, ssv = pl ? g.ss_ver : 0;
+    ScalePlane p = ScalePlane();
+    p.s = planes[pl];
+    p.sstride = (int) (src->p[pl].stride / (ptrdiff_t) sizeof(pixel));
+    p.swide = TILED || aligned_to(planes[pl], src->p[pl].stride, 8 * (int) sizeof(pixel));
+    p.pw = src->p[pl].w;
+    p.x0 = g.x0 >> ssh; p.y0 = g.y0 >> ssv; p.sw = (g.w + ssh) >> ssh; p.sh = (g.h + ssv) >> ssv;
+    p.dw = (g.dw + ssh) >> ssh; p.dh = (g.dh + ssv) >> ssv;
+    p.ow = p.sw <= 2LL * p.dw ? 128 : p.sw <= 4LL * p.dw ? 64 : 32;
+    p.oh = p.sh <= 4LL * p.dh ? 8 : 4;
+    return p;
+}
+
+// source luma rows from the top of the picture that destination rows [0, r1) of geometry g read (dav1d_hip_surface_scaled_rows_needed), r1 > 0
+inline int scale_rows_needed(const ScaleGeom &g, const int src_h, const int r1)
+{
+    long long need = g.y0 + ((long long) r1 * g.h + g.dh - 1) / g.dh;
+    if (!g.mono) {
+        const int sh = (g.h + g.ss_ver) >> g.ss_ver, dch = (g.dh + g.ss_ver) >> g.ss_ver, cr1 = r1 >= g.dh ? dch : r1 >> g.ss_ver;
+        const long long cneed = ((long long) (g.y0 >> g.ss_ver) + ((long long) cr1 * sh + dch - 1) / dch) << g.ss_ver;
+        if (cneed > need) need = cneed;
+    }
+    return (int) (need > src_h ? src_h : need);
 }
 
 } // namespace

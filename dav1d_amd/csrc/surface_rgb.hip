@@ -19,23 +19,6 @@
 
 namespace {
 
-// ---- output samples of channel ch (0, 1, 2 = R, G, B), and the opaque alpha of the sample type
-template <typename Base> struct RgbInt {
-    typedef typename Base::T T;
-    Base b; T alpha;
-    __device__ __forceinline__ T operator()(const int v, const int) const { return b(v); }
-};
-struct RgbF32 {
-    typedef float T;
-    float scale[3], bias[3]; T alpha;
-    __device__ __forceinline__ T operator()(const int v, const int ch) const { return dv::mul_add_2r((float) v, scale[ch], bias[ch]); }
-};
-struct RgbF16 {
-    typedef uint16_t T;
-    float scale[3], bias[3]; T alpha;
-    __device__ __forceinline__ T operator()(const int v, const int ch) const { return dv::f32_to_f16_bits(dv::mul_add_2r((float) v, scale[ch], bias[ch])); }
-};
-
 struct RgbxArgs {
     RgbArgs r;
     int ch;                 // rows of the chroma plane
@@ -43,26 +26,6 @@ struct RgbxArgs {
     int hf, vf;             // taps across / down other than replication
     int packed;             // samples a pixel in data[0] (3, 4), 0: planes
 };
-
-// N output samples to consecutive addresses, N * sizeof(T) any multiple of 8: vector stores of 16 bytes (8 where the run is no multiple of 16: 24 bytes
-// of uint8 RGB) where the destination allows and the run is whole, else the first n one by one
-template <typename T, int N>
-__device__ __forceinline__ void store_packed(T *const dst, const T (&t)[N], const int n, const bool wide)
-{
-    constexpr int BYTES = N * (int) sizeof(T), CH = BYTES % 16 ? 8 : 16;
-    static_assert(BYTES % CH == 0, "whole chunks");
-    if (wide && n >= N) {
-#pragma unroll
-        for (int i = 0; i < BYTES / CH; i++) {
-            Piece<CH> pc;
-            __builtin_memcpy(&pc, (const char *) t + i * CH, CH);
-            reinterpret_cast<Piece<CH> *>(dst)[i] = pc;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; i++) if (i < n) dst[i] = t[i];
-    }
-}
 
 // one sample of a plane (the same line request as the load8 around it)
 template <typename pixel, bool TILED>
@@ -251,14 +214,6 @@ int launch_rgbx(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, cons
     return hip_rc(hipGetLastError());
 }
 
-template <typename F> void set_float(F &o, const Dav1dHipRgbParams &p, const int bpc)
-{
-    for (int k = 0; k < 3; k++) {
-        o.scale[k] = p.normalize ? p.scale[k] : (float) (1.0 / (double) ((1 << bpc) - 1));
-        o.bias[k] = p.normalize ? p.bias[k] : 0.0f;          // (x + 0 is x: without normalisation this is OutF32's one multiply)
-    }
-}
-
 template <typename pixel, bool TILED>
 int launch_rgbx_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
                        const Dav1dHipRgbParams &p, const int row0, const int row1)
@@ -287,9 +242,7 @@ int rgbx_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *con
                     SurfaceCall *const call)
 {
     if (const int rc = surface_args_check(dst, src, row0, row1, call, false, true)) return rc;
-    if (dst->format < DAV1D_HIP_SURFACE_RGB_PLANAR) return -EINVAL;
-    if (p.chroma_pos < 0 || p.chroma_pos > 2) return -EINVAL;
-    if (p.normalize && dst->sample != DAV1D_HIP_SAMPLE_F32 && dst->sample != DAV1D_HIP_SAMPLE_F16) return -EINVAL;
+    if (const int rc = rgb_params_check(dst, p)) return rc;
     return 0;
 }
 

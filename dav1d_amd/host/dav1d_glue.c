@@ -71,6 +71,8 @@ typedef struct Hip {
     void (*fg_grain_destroy)(Dav1dHipContext *, Dav1dHipGrain *);
     int (*fg_apply_prepared)(Dav1dHipContext *, const Dav1dHipPicture *, const Dav1dHipPicture *, const Dav1dHipGrain *, int);
     int (*surface_export_rgb)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipRgbParams *, int, int);
+    int (*surface_export_rgb_scaled)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipSurfaceRect *, const Dav1dHipRgbParams *,
+                                     int, int);
     int (*frame_set_progress_callback)(Dav1dHipFrame *, void (*)(void *, int, const Dav1dHipPicture *), void *);
     int (*live_objects)(long long *);
     int (*device_count)(void);
@@ -751,6 +753,26 @@ int dav1d_hip_glue_output_rgb(Dav1dHipGlue *const g, const Dav1dPicture *const p
     return !rc ? 0 : no_mem ? DAV1D_ERR(ENOMEM) : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
 }
 
+/* The same at another size (dav1d_hip_surface_export_rgb_scaled): the rectangle `crop` of the picture (NULL: all of it) scaled down to dst->w x dst->h
+ * in the same pass.  `params` NULL as above.  No film grain: the call applies none.  Waits for the export like its siblings.  The library calls behind
+ * it are tested at the C ABI (tests/test_surface_rgb_scaled.py mirrors the call sequence). */
+int dav1d_hip_glue_output_rgb_scaled(Dav1dHipGlue *const g, const Dav1dPicture *const pic, const Dav1dHipSurface *const dst,
+                                     const Dav1dHipSurfaceRect *const crop, const Dav1dHipRgbParams *const params) {
+    if (!g || !pic || !pic->allocator_data || !dst) return DAV1D_ERR(EINVAL);
+    const Dav1dHipGluePicture *const hp = pic->allocator_data;
+    Dav1dHipRgbParams p;
+    memset(&p, 0, sizeof(p));
+    if (params) p = *params;
+    else p.chroma_pos = pic->seq_hdr->chr == DAV1D_CHR_COLOCATED ? 2 : 1;
+    Dav1dHipContext *const ctx_out = g->dev[hp->ref_dev].ctx_out;
+    const int thread_dev = borrow_thread(g, ctx_out);
+    int rc = g->hip.surface_export_rgb_scaled(ctx_out, dst, &hp->ref, crop, &p, 0, dst->h);
+    const int bad_args = rc == -EINVAL || rc == -ENOTSUP;
+    if (!rc) rc = g->hip.sync(ctx_out);
+    return_thread(g, thread_dev);
+    return !rc ? 0 : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
+}
+
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *const g) { return g ? atomic_load(&g->n_backend_failures) : 0; }
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *const g) { return g ? atomic_load(&g->n_row_publications) : 0; }
 int dav1d_hip_glue_devices(const Dav1dHipGlue *const g) { return g ? g->n_dev : 0; }
@@ -790,7 +812,7 @@ int dav1d_hip_glue_create(Dav1dHipGlue **const out, const Dav1dHipGlueOptions *c
     SYM(fg_apply, "dav1d_hip_fg_apply"); SYM(picture_alloc, "dav1d_hip_picture_alloc"); SYM(picture_free, "dav1d_hip_picture_free");
     SYM(plane_download, "dav1d_hip_plane_download"); SYM(surface_export, "dav1d_hip_surface_export"); SYM(surface_export_grain, "dav1d_hip_surface_export_grain");
     SYM(fg_prepare, "dav1d_hip_fg_prepare"); SYM(fg_grain_destroy, "dav1d_hip_fg_grain_destroy"); SYM(fg_apply_prepared, "dav1d_hip_fg_apply_prepared");
-    SYM(surface_export_rgb, "dav1d_hip_surface_export_rgb"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
+    SYM(surface_export_rgb, "dav1d_hip_surface_export_rgb"); SYM(surface_export_rgb_scaled, "dav1d_hip_surface_export_rgb_scaled"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
     SYM(live_objects, "dav1d_hip_live_objects"); SYM(device_count, "dav1d_hip_device_count"); SYM(use, "dav1d_hip_context_use");
     SYM(enable_peer_access, "dav1d_hip_enable_peer_access"); SYM(current_device, "dav1d_hip_current_device"); SYM(set_device, "dav1d_hip_set_device");
     SYM(picture_copy_peer, "dav1d_hip_picture_copy_peer"); SYM(picture_copy_peer_rows, "dav1d_hip_picture_copy_peer_rows"); SYM(picture_retile, "dav1d_hip_picture_retile");

@@ -106,6 +106,10 @@ int dav1d_hip_glue_output_surface(Dav1dHipGlue *g, const Dav1dPicture *pic, cons
  * NULL: chroma_pos from pic->seq_hdr->chr (DAV1D_CHR_COLOCATED: 2, DAV1D_CHR_VERTICAL and DAV1D_CHR_UNKNOWN: 1), no normalisation.  With grain: two
  * passes, the grain into a temporary picture and the export from that.  Returns when the surface is written. */
 int dav1d_hip_glue_output_rgb(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, const Dav1dHipRgbParams *params, int apply_grain);
+/* ---- ... and at another size (dav1d_hip_surface_export_rgb_scaled): `crop` (NULL: the whole picture) scaled down to dst->w x dst->h, the scaled
+ * chroma upsampled at its site, in one pass.  `params` NULL as above.  No film grain.  Returns when the surface is written. */
+int dav1d_hip_glue_output_rgb_scaled(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, const Dav1dHipSurfaceRect *crop,
+                                     const Dav1dHipRgbParams *params);
 
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *g);    /* frames that failed INSIDE the backend (not: frames dav1d rejects) */
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *g);

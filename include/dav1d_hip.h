@@ -235,14 +235,14 @@ enum Dav1dHipSurfaceFormat {
     DAV1D_HIP_SURFACE_PLANAR     = 0,  /* data[0..2] = Y, U, V (I400: Y only) */
     DAV1D_HIP_SURFACE_SEMIPLANAR = 1,  /* data[0] = Y, data[1] = U,V interleaved (NV12 / P010 family; I400: Y only) */
     DAV1D_HIP_SURFACE_RGB_PLANAR = 2,  /* data[0..2] = R, G, B, each at luma size */
-    DAV1D_HIP_SURFACE_RGB_PACKED = 3,  /* data[0]: R,G,B interleaved, 3 samples a pixel (dav1d_hip_surface_export_rgb only) */
-    DAV1D_HIP_SURFACE_RGBA_PACKED = 4, /* data[0]: R,G,B,A interleaved, A = opaque (dav1d_hip_surface_export_rgb only) */
+    DAV1D_HIP_SURFACE_RGB_PACKED = 3,  /* data[0]: R,G,B interleaved, 3 samples a pixel (dav1d_hip_surface_export_rgb and _rgb_scaled only) */
+    DAV1D_HIP_SURFACE_RGBA_PACKED = 4, /* data[0]: R,G,B,A interleaved, A = opaque (dav1d_hip_surface_export_rgb and _rgb_scaled only) */
 };
 enum Dav1dHipSurfaceSample {
     DAV1D_HIP_SAMPLE_NATIVE = 0,       /* uint8 at 8 bpc, uint16 with the value in the LOW bits at 10 / 12 bpc */
     DAV1D_HIP_SAMPLE_MSB16  = 1,       /* uint16, value << (16 - bpc): P010 / P012 / P210 / P410; 8 bpc: -EINVAL */
     DAV1D_HIP_SAMPLE_F32    = 2,       /* float, (float) value * (1.0f / ((1 << bpc) - 1)): one float multiply */
-    DAV1D_HIP_SAMPLE_F16    = 3,       /* IEEE binary16 of the float32 value, round to nearest even (dav1d_hip_surface_export_rgb only) */
+    DAV1D_HIP_SAMPLE_F16    = 3,       /* IEEE binary16 of the float32 value, round to nearest even (dav1d_hip_surface_export_rgb and _rgb_scaled only) */
 };
 typedef struct Dav1dHipSurface {
     void *data[3];        /* DEVICE memory of the caller (dav1d_hip_malloc, a torch tensor, ...) on the context's device */
@@ -323,6 +323,29 @@ typedef struct Dav1dHipRgbParams {
 DAV1D_HIP_API int dav1d_hip_surface_export_rgb(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
                                                const Dav1dHipRgbParams *params /* NULL = all zero */, int row0, int row1);
 DAV1D_HIP_API int dav1d_hip_surface_rgb_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipRgbParams *params, int row1);
+/* Tensor-ready RGB through the crop and the scaler (dav1d_amd/csrc/surface_rgb_scale.hip): the two calls above in one pass.  Let Q be
+ * the picture of dst->w x dst->h samples, of src's layout and bpc, whose planes are the scaled planes of dav1d_hip_surface_export_scaled (the same crop
+ * rule, the same window per plane, the scaler S).  The call writes byte for byte what dav1d_hip_surface_export_rgb(c, dst, Q, params, drow0, drow1)
+ * would write: formats RGB_PLANAR, RGB_PACKED, RGBA_PACKED; samples NATIVE, MSB16, F32, F16; chroma_pos 0, 1, 2 upsamples Q's chroma planes, cl() clamps
+ * against Q's chroma size (no sample outside the crop is read for it); normalisation, alpha, matrix, range and the matrix-0 rule as there.  With
+ * chroma_pos 0, RGB_PLANAR and a sample other than F16 these are the bytes of dav1d_hip_surface_export_scaled.  Q itself never reaches memory.
+ * A limitation, by definition: S treats a chroma sample as the box over its 2 x 2 (2 x 1) luma samples, so Q's chroma lies up to half a SOURCE luma
+ * sample away from the site chroma_pos names; a phase-corrected chroma scaler is not built.  No film grain.
+ * [drow0, drow1) are DESTINATION luma rows (clamped to the surface; both multiples of 2 unless they are the surface's end); a band writes the bytes of
+ * the whole-surface call.  dav1d_hip_surface_rgb_scaled_rows_needed is host arithmetic: dav1d_hip_surface_scaled_rows_needed for destination rows
+ * [0, r), r = min(dst->h, drow1 + 2) when ss_ver == 1 and chroma_pos != 0, else min(dst->h, drow1) (0 for drow1 <= 0); a negative errno for what the
+ * export would refuse.
+ * Asynchronous exactly like its parents: one launch on the context's stream, dav1d_hip_last_kernel_ms reports its device time, `src` is const and a
+ * DAV1D_HIP_TWIN_ONLY picture stays one, no allocation, no host wait, no table made on the host, nothing written outside the visible destination
+ * samples of the rows asked for.
+ * Errors, before anything is enqueued: what either parent refuses, with its code: -EINVAL for a format below RGB_PLANAR, chroma_pos outside 0..2,
+ * normalize != 0 with an integer sample, MSB16 at 8 bpc, matrix 0 with a layout other than 4:4:4, a crop outside the picture, an empty crop, an odd
+ * x0 / y0 on a subsampled axis, odd band rows; -ENOTSUP for upscaling, ratios above 8 and other matrix codes; -EXDEV for a picture of another device. */
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_scaled(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                      const Dav1dHipSurfaceRect *crop /* NULL = everything */,
+                                                      const Dav1dHipRgbParams *params /* NULL = all zero */, int drow0, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_rgb_scaled_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
+                                                           const Dav1dHipRgbParams *params, int drow1);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -17,6 +17,9 @@ timed the same way in the same run.
 --rgb: dav1d_hip_surface_export_rgb (sited chroma, packed RGB / RGBA, binary16) against dav1d_hip_surface_export to RGB planes of the same sample
 type in the same run (binary16: the float32 export); where a variant writes more bytes than its yardstick (RGBA: 4/3 of the writes) the
 yardstick's times are scaled by the bytes moved.
+--rgb-scaled: dav1d_hip_surface_export_rgb_scaled at 2:1, 4:1 and as a 224 x 224 centre crop at 8:1, each as packed RGBA float16 normalised at
+chroma_pos 1 and as planar float16 at chroma_pos 0, against the route a user pays today, timed the same way in the same run on the same pictures:
+dav1d_hip_surface_export_scaled to planar native into a pre-allocated picture of the output size, then dav1d_hip_surface_export_rgb from it.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -250,12 +253,80 @@ def rgb_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def rgb_scaled_runs(a, ctx, ev, pics, src_bytes):
+    """the one call against export_scaled into a picture-shaped buffer + export_rgb from it, per ratio and output variant"""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    mx = (1 << bpc) - 1
+    scale, bias = [1.0 / (mx * s) for s in (0.229, 0.224, 0.225)], [-m / s for m, s in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))]
+    side = min(w, h, 8 * 224)
+    geoms = [("2:1", None, (w // 2, h // 2)), ("4:1", None, (w // 4, h // 4)),
+             ("%d:1 centre crop" % (side // 224), (((w - side) // 2) & ~1, ((h - side) // 2) & ~1, side, side), (224, 224))]
+    outs = [("packed RGBA float16 normalised, chroma_pos 1", api.SURFACE_RGBA_PACKED, 4, 1, scale, bias),
+            ("planar float16, chroma_pos 0", api.SURFACE_RGB_PLANAR, 3, 0, None, None)]
+    runs, frees = [], []
+    for gname, crop, (dw, dh) in geoms:
+        cw, ch = (dw + 1) // 2, (dh + 1) // 2
+        sw, sh = (crop[2], crop[3]) if crop else (w, h)
+        read = 2 * (sw * sh + 2 * ((sw + 1) // 2) * ((sh + 1) // 2))
+        mid = 2 * (dw * dh + 2 * cw * ch)
+        tmps = [ctx.picture(dw, dh, layout, bpc) for _ in range(a.pairs)]
+        views = [api.Surface.wrap(ctx, [t.pic.p[pl].data for pl in range(3)], [t.pic.p[pl].stride for pl in range(3)], dw, dh, layout, bpc,
+                                  api.SURFACE_PLANAR, api.SAMPLE_NATIVE) for t in tmps]
+        frees += tmps
+        for oname, fmt, n, pos, sc, bi in outs:
+            surfs = [ctx.surface(dw, dh, layout, bpc, fmt, api.SAMPLE_F16) for _ in range(a.pairs)]
+            frees += surfs
+            out_bytes = n * 2 * dw * dh
+
+            def two_calls(k, surfs=surfs, tmps=tmps, views=views, crop=crop, pos=pos, sc=sc, bi=bi):
+                pics[k % a.pairs].export_scaled(views[k % a.pairs], crop)
+                tmps[k % a.pairs].export_rgb(surfs[k % a.pairs], pos, sc, bi)
+
+            def fused(k, surfs=surfs, crop=crop, pos=pos, sc=sc, bi=bi):
+                pics[k % a.pairs].export_rgb_scaled(surfs[k % a.pairs], crop, pos, sc, bi)
+            yard = "export_scaled + export_rgb %s (%dx%d): %s" % (gname, dw, dh, oname)
+            runs.append((yard, read + 2 * mid + out_bytes, two_calls, None))
+            runs.append(("export_rgb_scaled %s (%dx%d): %s" % (gname, dw, dh, oname), read + out_bytes, fused, yard))
+    print("# surface_bench --rgb-scaled on %s: %dx%d 4:2:0 %d-bit twin-only sources, %d picture / surface pairs in rotation, 20 warm-up + %d timed calls per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, a.pairs, a.calls, a.repeats))
+    print("# bytes per call = bytes read + bytes written, from the shapes (the yardstick writes and reads the scaled planes once more)")
+    results = {r[0]: [] for r in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, call, _ in runs:
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            print("repeat %d  %-96s %8.4f ms/call  %7.1f MB/call  %7.0f GB/s" % (rep, name, ms, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (min / median / max ms per call over the repeats)")
+    for name, nbytes, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-96s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(results[name]), sorted(results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-96s median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms: %s"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met"))
+    for s in frees:
+        s.free()
+    for p in pics:
+        p.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
     ap.add_argument("--grain", action="store_true", help="the fused grain + export variants against fg_apply_prepared + export")
     ap.add_argument("--scaled", action="store_true", help="dav1d_hip_surface_export_scaled at 2:1 and 4:1 against the plain export at full size")
     ap.add_argument("--rgb", action="store_true", help="dav1d_hip_surface_export_rgb (sited chroma, packed, float16) against the plain export to RGB planes")
+    ap.add_argument("--rgb-scaled", action="store_true", help="dav1d_hip_surface_export_rgb_scaled against export_scaled into a picture + export_rgb from it")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -291,6 +362,8 @@ def main():
         return scaled_runs(a, ctx, ev, pics, variants[:3], src_bytes)
     if a.rgb:
         return rgb_runs(a, ctx, ev, pics, src_bytes)
+    if a.rgb_scaled:
+        return rgb_scaled_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
