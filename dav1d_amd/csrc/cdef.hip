@@ -276,6 +276,10 @@ __global__ __launch_bounds__(64) void cdef_kernel(const DevPlanes dst, const Dev
         if (run && y < lh) {
             const int v = cdef_px(tmp, x, y, pri, sec, d, damping, bitdepth_min_8);
             reinterpret_cast<pixel *>(dst.data[lpl])[(y0 + y) * dst.stride[lpl] + x0 + x] = (pixel) v;
+        } else if (!raw) {
+            // a listed unit that does not filter luma still gets its block: every listed unit is WRITTEN, as in the strip kernel
+            // (dst holds a copy of src under the unlisted units only)
+            reinterpret_cast<pixel *>(dst.data[0])[(y0 + y) * dst.stride[0] + x0 + x] = sy[(y0 + y) * src.stride[0] + x0 + x];
         }
     }
 
@@ -315,6 +319,17 @@ __global__ __launch_bounds__(64) void cdef_kernel(const DevPlanes dst, const Dev
             const int x = k & (w - 1), y = k >> (3 - ss_hor);
             const int v = cdef_px(pl == 1 ? tmp : tmp2, x, y, t.uv_pri, t.uv_sec, uvdir, damping - 1, bitdepth_min_8);
             reinterpret_cast<pixel *>(dst.data[pl])[(cy0 + y) * dst.stride[pl] + cx0 + x] = (pixel) v;
+        }
+    } else if (!raw && layout != DAV1D_HIP_LAYOUT_I400) {
+        // neither chroma strength: the listed unit's chroma blocks go across as they are
+        const int ss_ver = layout == DAV1D_HIP_LAYOUT_I420, ss_hor = layout != DAV1D_HIP_LAYOUT_I444;
+        const int w = 8 >> ss_hor, npx = w * (8 >> ss_ver);
+        const int cx0 = x0 >> ss_hor, cy0 = y0 >> ss_ver;
+        for (int i = lane; i < 2 * npx; i += 64) {
+            const int pl = 1 + (i >= npx), k = i - (pl - 1) * npx;
+            const int x = k & (w - 1), y = k >> (3 - ss_hor);
+            reinterpret_cast<pixel *>(dst.data[pl])[(cy0 + y) * dst.stride[pl] + cx0 + x] =
+                reinterpret_cast<const pixel *>(src.data[pl])[(cy0 + y) * src.stride[pl] + cx0 + x];
         }
     }
 }
