@@ -28,6 +28,9 @@ class Surface(C.Structure):            # == Dav1dHipSurface
                 ("matrix", C.c_int), ("full_range", C.c_int)]
 
 
+SURFACE_BATCH_MAX = 1024               # DAV1D_HIP_SURFACE_BATCH_MAX
+
+
 class SurfaceRect(C.Structure):        # == Dav1dHipSurfaceRect
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
 
@@ -95,7 +98,7 @@ SYMBOLS = [
     "dav1d_hip_lister_mask_offset", "dav1d_hip_lister_tables", "dav1d_hip_lister_block_warp", "dav1d_hip_lister_filter_sbrow",
     "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain", "dav1d_hip_surface_export_scaled", "dav1d_hip_surface_scaled_rows_needed",
     "dav1d_hip_surface_export_rgb", "dav1d_hip_surface_rgb_rows_needed",
-    "dav1d_hip_surface_export_rgb_scaled", "dav1d_hip_surface_rgb_scaled_rows_needed",
+    "dav1d_hip_surface_export_rgb_scaled", "dav1d_hip_surface_rgb_scaled_rows_needed", "dav1d_hip_surface_export_rgb_scaled_batch",
 ]
 
 
@@ -301,6 +304,7 @@ def load(path=None):
         "dav1d_hip_surface_export_rgb": (i, [vp, P(Surface), P(Picture), P(RgbParams), i, i]),
         "dav1d_hip_surface_rgb_rows_needed": (i, [P(Surface), P(Picture), P(RgbParams), i]),
         "dav1d_hip_surface_export_rgb_scaled": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
+        "dav1d_hip_surface_export_rgb_scaled_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), P(i)]),
         "dav1d_hip_surface_rgb_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),

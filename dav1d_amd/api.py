@@ -334,6 +334,49 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     return s
 
 
+def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sample=None, chroma_pos=None, scale=None, bias=None):
+    """Fills one torch tensor with N pictures (or N regions: pictures may repeat) through Context.export_rgb_scaled_batch, one launch for all of them:
+    `tensor` of shape (N, 3, h, w) gets R, G, B planes, (N, h, w, 3) / (N, h, w, 4) gets packed RGB / RGBA; h x w is the output size of every item and
+    crops[k] = (x0, y0, w, h) (`crops` None: the whole picture) the rectangle of pics[k] that is scaled to it.  The dtype picks the sample as in
+    export_to_tensor (float32: F32, float16: F16, else `sample`, native by default).  Item k is written through tensor[k]: any batch stride is fine
+    (a view such as big[::2]), rows need unit stride.  ValueError for what export_to_tensor raises, for len(pics) != N, and for a shape
+    (N, 3, n, 3) or (N, 3, n, 4), which reads both ways.  Returns the surfaces."""
+    if tensor.dim() != 4:
+        raise ValueError("a batch tensor has shape (N, 3, h, w), (N, h, w, 3) or (N, h, w, 4)")
+    shape = tuple(int(v) for v in tensor.shape)
+    n = shape[0]
+    if len(pics) != n or (crops is not None and len(crops) != n):
+        raise ValueError("a tensor of shape %s takes %d pictures, and %d crops if any" % (shape, n, n))
+    chw, hwc = shape[1] == 3, shape[3] in (3, 4)
+    if chw and hwc:
+        raise ValueError("a tensor of shape %s can be read as (N, 3, h, w) and as (N, h, w, 3 or 4): not accepted" % (shape,))
+    if not chw and not hwc:
+        raise ValueError("a batch tensor has shape (N, 3, h, w), (N, h, w, 3) or (N, h, w, 4)")
+    if not tensor.is_cuda:
+        raise ValueError("export_batch_to_tensor needs a device tensor")
+    if tensor.stride(-1) != 1:
+        raise ValueError("export_batch_to_tensor needs unit stride along a row")
+    if hwc and tensor.stride(2) != shape[3]:
+        raise ValueError("a packed RGB tensor has its channels next to each other")
+    if sample is None:
+        import torch
+        sample = SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_F16 if tensor.dtype == torch.float16 else SAMPLE_NATIVE
+    es = tensor.element_size()
+    h, w = (shape[1], shape[2]) if hwc else (shape[2], shape[3])
+    fmt = SURFACE_RGB_PLANAR if chw else SURFACE_RGB_PACKED if shape[3] == 3 else SURFACE_RGBA_PACKED
+    surfaces = []
+    for k, pic in enumerate(pics):
+        t = tensor[k]
+        ptrs, strides = ([t.data_ptr()], [t.stride(0) * es]) if hwc else ([t[c].data_ptr() for c in range(3)], [t.stride(1) * es] * 3)
+        s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
+        if s.dtype.itemsize != es:
+            raise ValueError("tensor dtype does not fit the surface of item %d: %s" % (k, s.dtype))
+        surfaces.append(s)
+    if n:
+        pics[0].ctx.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos or 0, scale, bias)
+    return surfaces
+
+
 class _List:
     def __init__(self, ctx, kind, tasks, dtype):
         self.ctx, self.kind = ctx, kind
@@ -475,6 +518,22 @@ class Context:
 
     def last_kernel_ms(self):
         return float(self.lib.dav1d_hip_last_kernel_ms(self.h))
+
+    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None):
+        """dav1d_hip_surface_export_rgb_scaled_batch: item k gets what pics[k].export_rgb_scaled(surfaces[k], crops[k], chroma_pos, scale, bias) writes,
+        all items in one launch (two when raster and twin-only pictures are mixed).  Pictures may repeat; `crops` is None (every item whole) or a
+        rectangle (x0, y0, w, h) per item.  One format, one sample type and one pixel size (8 bit, or 10 / 12 bit) per batch.  Asynchronous like
+        export; a HipError names the item that was refused."""
+        n = len(surfaces)
+        if len(pics) != n or (crops is not None and len(crops) != n):
+            raise ValueError("a batch takes one picture, and one crop if any, per surface")
+        dst = (SurfaceDesc * max(n, 1))(*[s.desc for s in surfaces])
+        src = (C.POINTER(Picture) * max(n, 1))(*[C.pointer(q.pic) for q in pics])
+        rects = None if crops is None else (SurfaceRect * max(n, 1))(*[SurfaceRect(*[int(v) for v in r]) for r in crops])
+        p = DevicePicture._rgb_params(chroma_pos, scale, bias)
+        bad = C.c_int(-1)
+        rc = self.lib.dav1d_hip_surface_export_rgb_scaled_batch(self.h, n, dst, src, rects, C.byref(p), C.byref(bad))
+        _chk(rc, "surface_export_rgb_scaled_batch" + (" (item %d)" % bad.value if bad.value >= 0 else ""))
 
     # ---- batched entry points (host task arrays, device arenas)
     def itx_add_batch(self, dst, tasks, coef):

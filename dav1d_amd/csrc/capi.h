@@ -83,6 +83,14 @@ struct Dav1dHipContext {
     hipEvent_t ev_retile;       // the end of the most recent overlapped retile (dav1d_hip_picture_retile_overlapped) ...
     bool retile_pending;        // ... which the next launches that read twins have to wait for
     std::mutex run_mtx;         // one multi-stream section (recon list run, banded post filters) at a time per context
+    // the item tables of dav1d_hip_surface_export_rgb_scaled_batch (surface_batch.hip): a ring of staging slots, pinned host memory and its device copy,
+    // each reused once the event behind the launches that read it has passed; slots grow on demand, dav1d_hip_close frees them and the outgrown ones
+    enum { N_BATCH_STAGE = 4 };
+    struct BatchStage { uint8_t *host, *dev; size_t cap; hipEvent_t done; bool made, busy; };
+    BatchStage batch_stage[N_BATCH_STAGE] = {};
+    unsigned batch_next = 0;
+    std::vector<void *> batch_retired_host, batch_retired_dev;
+    std::vector<uint8_t> batch_plan;            // what the checks of a batch found per item, kept for the pass that fills the table (grows to the largest batch)
 };
 
 // Device memory for the task list of one *_batch call, taken from a pool of the context.  hipMalloc + hipFree per call was the

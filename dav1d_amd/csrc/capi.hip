@@ -168,6 +168,13 @@ void dav1d_hip_close(Dav1dHipContext *c) {
     for (const Dav1dHipContext::Arena &ar : c->free_arenas) hipFree(ar.dev);
     for (const Dav1dHipContext::Arena &ar : c->free_task_bufs) hipFree(ar.dev);
     for (Dav1dHipPicture &q : c->free_pictures) { if (q.alloc) hipFree(q.alloc); if (q.twin_alloc) hipFree(q.twin_alloc); }
+    for (Dav1dHipContext::BatchStage &bs : c->batch_stage) {
+        if (bs.made) hipEventDestroy(bs.done);
+        if (bs.host) hipHostFree(bs.host);
+        if (bs.dev) hipFree(bs.dev);
+    }
+    for (void *q : c->batch_retired_host) hipHostFree(q);
+    for (void *q : c->batch_retired_dev) hipFree(q);
     if (c->gather_dev) hipFree(c->gather_dev);
     if (c->segtab_dev) hipFree(c->segtab_dev);
     if (c->pending_slab) hipHostFree(c->pending_slab);

@@ -346,6 +346,27 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_scaled(Dav1dHipContext *c, const 
                                                       const Dav1dHipRgbParams *params /* NULL = all zero */, int drow0, int drow1);
 DAV1D_HIP_API int dav1d_hip_surface_rgb_scaled_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                            const Dav1dHipRgbParams *params, int drow1);
+/* Many of those exports in one launch (dav1d_amd/csrc/surface_batch.hip).  For every item i < n the call writes the bytes, at the
+ * addresses, that dav1d_hip_surface_export_rgb_scaled(c, &dst[i], src[i], crop ? &crop[i] : NULL, params, 0, dst[i].h) writes, and no other byte: whole
+ * surfaces, no bands.  Items are independent: sources may repeat (several crops of one picture) and may differ in size, layout, bit depth and picture
+ * state (raster planes valid or DAV1D_HIP_TWIN_ONLY, which they stay); output sizes, strides, matrix and range are each surface's own.  Uniform over the
+ * batch, because they select the kernel: dst[i].format, dst[i].sample and the pixel size of the sources (all 8 bit, or all 10 / 12 bit).  One `params`
+ * serves all items.  Destinations that overlap are the caller's error and are not checked.
+ * Asynchronous like the single call: one launch on the context's stream (two when raster and twin-only sources are mixed), between the events
+ * dav1d_hip_last_kernel_ms reads.  The items go to the device through a table in memory of the context (a small ring of staging slots, grown on
+ * demand, freed by dav1d_hip_close): the caller's arrays may be reused as soon as the call returns, the call may be made again before the last batch
+ * has run, and in the steady state it neither allocates nor waits for the device (it waits only when every slot of the ring is still in flight).
+ * Calls on one context come from one thread at a time.
+ * Errors, before anything is enqueued and before any byte is written; *bad_item (if not NULL) is the item at fault, -1 where the call as a whole is:
+ * n == 0 returns 0 and does nothing; -EINVAL for a NULL c, n < 0, n > DAV1D_HIP_SURFACE_BATCH_MAX, NULL dst or src, a NULL src[i] (*bad_item = the first
+ * such i, found before any item is looked at); then, in item order, what the single call refuses for the item, with its code, and -EINVAL for an item
+ * whose format, sample or pixel size differs from item 0's. */
+#define DAV1D_HIP_SURFACE_BATCH_MAX 1024
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_scaled_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst /* [n] */,
+                                                            const Dav1dHipPicture *const *src /* [n] */,
+                                                            const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
+                                                            const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */,
+                                                            int *bad_item /* may be NULL */);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -20,6 +20,11 @@ yardstick's times are scaled by the bytes moved.
 --rgb-scaled: dav1d_hip_surface_export_rgb_scaled at 2:1, 4:1 and as a 224 x 224 centre crop at 8:1, each as packed RGBA float16 normalised at
 chroma_pos 1 and as planar float16 at chroma_pos 0, against the route a user pays today, timed the same way in the same run on the same pictures:
 dav1d_hip_surface_export_scaled to planar native into a pre-allocated picture of the output size, then dav1d_hip_surface_export_rgb from it.
+--batch: dav1d_hip_surface_export_rgb_scaled_batch against the N single dav1d_hip_surface_export_rgb_scaled calls it replaces, issued back to back with
+one pair of events around the N calls, in the same run on the same pictures and destinations; both sides call the library with argument arrays made
+once.  (a) N = 8 and N = 32 distinct pictures, the 1792 x 1792 centre crop to 224 x 224; (b) N = 32 crops of ONE picture, tiled over the frame, to 224 x 224;
+(c) N = 8 pictures at 4:1; (d) one 4:1 item and 31 of the 224 x 224 items.  (a) to (c) as packed RGBA float16 normalised at chroma_pos 1 and as planar
+float16 at chroma_pos 0.  The 32 pictures share one host image (their device memory is their own): the time does not depend on the pixels.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -320,6 +325,86 @@ def rgb_scaled_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def batch_runs(a, ctx, ev, pics):
+    """one batch call against the N single calls it replaces, per variant and output"""
+    from dav1d_amd._lib import Picture, RgbParams, Surface as SurfaceDesc
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    lib = ctx.lib
+    mx = (1 << bpc) - 1
+    scale, bias = [1.0 / (mx * s) for s in (0.229, 0.224, 0.225)], [-m / s for m, s in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))]
+    side = min(w, h, 8 * 224)
+    centre = (((w - side) // 2) & ~1, ((h - side) // 2) & ~1, side, side)
+    nx = 8
+    ny = 32 // nx
+    tiles = [(((w // nx) & ~1) * (k % nx), ((h // ny) & ~1) * (k // nx), (w // nx) & ~1, (h // ny) & ~1) for k in range(32)]
+    whole, quarter, thumb = (0, 0, w, h), (w // 4, h // 4), (224, 224)
+    n_pics = len(pics)
+    variants = [("(a) %d pictures, centre crop to 224x224" % n, [(pics[k % n_pics], centre, thumb) for k in range(n)]) for n in (8, 32)]
+    variants.append(("(b) 32 crops of one picture to 224x224", [(pics[0], tiles[k], thumb) for k in range(32)]))
+    variants.append(("(c) 8 pictures at 4:1 (%dx%d)" % quarter, [(pics[k % n_pics], whole, quarter) for k in range(8)]))
+    mixed = ("(d) one 4:1 item and 31 of 224x224", [(pics[0], whole, quarter)] + [(pics[k % n_pics], centre, thumb) for k in range(1, 32)])
+    outs = [("packed RGBA float16 normalised, chroma_pos 1", api.SURFACE_RGBA_PACKED, 4, 1, scale, bias),
+            ("planar float16, chroma_pos 0", api.SURFACE_RGB_PLANAR, 3, 0, None, None)]
+    runs, frees = [], []
+    for vname, items in variants + [mixed]:
+        for oname, fmt, nch, pos, sc, bi in outs[:1] if items is mixed[1] else outs:
+            n = len(items)
+            sizes = [nch * 2 * dw * dh for _, _, (dw, dh) in items]
+            buf = ctx.buffer(sum(sizes))
+            frees.append(buf)
+            dst, at = (SurfaceDesc * n)(), 0
+            for k, (_, _, (dw, dh)) in enumerate(items):          # item k behind item k - 1 in one buffer: (N, h, w, 4) or (N, 3, h, w) where the sizes agree
+                planes = [buf.ptr + at] if fmt == api.SURFACE_RGBA_PACKED else [buf.ptr + at + c * 2 * dw * dh for c in range(3)]
+                dst[k] = api.Surface.wrap(ctx, planes, [nch * 2 * dw] if fmt == api.SURFACE_RGBA_PACKED else [2 * dw] * 3, dw, dh, layout, bpc, fmt, api.SAMPLE_F16).desc
+                at += sizes[k]
+            src = (C.POINTER(Picture) * n)(*[C.pointer(p.pic) for p, _, _ in items])
+            rects = (api.SurfaceRect * n)(*[api.SurfaceRect(*crop) for _, crop, _ in items])
+            params = api.DevicePicture._rgb_params(pos, sc, bi)
+            single_args = [(ctx.h, C.byref(dst[k]), src[k], C.byref(rects[k]), C.byref(params), 0, dst[k].h) for k in range(n)]
+
+            def singles(_, args=single_args, f=lib.dav1d_hip_surface_export_rgb_scaled):
+                for t in args:
+                    assert f(*t) == 0
+
+            def batch(_, n=n, dst=dst, src=src, rects=rects, params=params, f=lib.dav1d_hip_surface_export_rgb_scaled_batch):
+                assert f(ctx.h, n, dst, src, rects, C.byref(params), None) == 0
+            read = sum(2 * (cr[2] * cr[3] + 2 * ((cr[2] + 1) // 2) * ((cr[3] + 1) // 2)) for _, cr, _ in items)
+            yard = "%d single calls %s: %s" % (n, vname, oname)
+            runs.append((yard, read + sum(sizes), singles, None))
+            runs.append(("one batch call %s: %s" % (vname, oname), read + sum(sizes), batch, yard))
+    print("# surface_bench --batch on %s: %dx%d 4:2:0 %d-bit twin-only sources, %d pictures, 20 warm-up + %d timed repetitions per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, n_pics, a.calls, a.repeats))
+    print("# a repetition is ONE batch call or the N single calls it replaces, between one pair of events; bytes = bytes read + bytes written, from the shapes")
+    results = {r[0]: [] for r in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, call, _ in runs:
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            print("repeat %d  %-110s %8.4f ms/batch  %7.1f MB  %7.0f GB/s" % (rep, name, ms, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (min / median / max ms per batch over the repeats)")
+    for name, nbytes, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-110s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(results[name]), sorted(results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-110s median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms: %s (x %.2f)"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met", u[len(u) // 2] / v[len(v) // 2]))
+    for s in frees:
+        s.free()
+    for p in pics:
+        p.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
@@ -327,6 +412,7 @@ def main():
     ap.add_argument("--scaled", action="store_true", help="dav1d_hip_surface_export_scaled at 2:1 and 4:1 against the plain export at full size")
     ap.add_argument("--rgb", action="store_true", help="dav1d_hip_surface_export_rgb (sited chroma, packed, float16) against the plain export to RGB planes")
     ap.add_argument("--rgb-scaled", action="store_true", help="dav1d_hip_surface_export_rgb_scaled against export_scaled into a picture + export_rgb from it")
+    ap.add_argument("--batch", action="store_true", help="dav1d_hip_surface_export_rgb_scaled_batch against the N single calls it replaces")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -340,12 +426,14 @@ def main():
     ctx = api.Context(0)
     ev = Events(ctx.lib.dav1d_hip_stream(ctx.h))
     rng = np.random.default_rng(1)
-    pics = []
-    for _ in range(a.pairs):
+    pics, shared = [], {}
+    for _ in range(32 if a.batch else a.pairs):
         p = ctx.picture(w, h, layout, bpc)
         for pl in range(3):
             shape = p.padded_shape(pl)
-            p.upload(pl, rng.integers(0, 1 << bpc, size=shape, dtype=np.uint16))
+            if not a.batch or pl not in shared:
+                shared[pl] = rng.integers(0, 1 << bpc, size=shape, dtype=np.uint16)
+            p.upload(pl, shared[pl])
         p.retile()
         p.pic.twin_ok = api.TWIN_ONLY
         pics.append(p)
@@ -364,6 +452,8 @@ def main():
         return rgb_runs(a, ctx, ev, pics, src_bytes)
     if a.rgb_scaled:
         return rgb_scaled_runs(a, ctx, ev, pics, src_bytes)
+    if a.batch:
+        return batch_runs(a, ctx, ev, pics)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
