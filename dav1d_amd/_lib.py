@@ -39,6 +39,13 @@ class RgbParams(C.Structure):         # == Dav1dHipRgbParams
     _fields_ = [("chroma_pos", C.c_int), ("normalize", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
+COLOUR_ENC_N = 15361                   # DAV1D_HIP_COLOUR_ENC_N: binary16 patterns 0x0000 .. 0x3C00
+
+
+class ColourDesc(C.Structure):         # == Dav1dHipColourDesc
+    _fields_ = [("bpc", C.c_int), ("lin", C.POINTER(C.c_float)), ("has_matrix", C.c_int), ("m", C.c_float * 9), ("enc", C.POINTER(C.c_uint16))]
+
+
 class HostPicture(C.Structure):
     _fields_ = [("data", C.c_void_p * 3), ("stride", C.c_ssize_t * 2), ("dev", Picture), ("alloc", C.c_void_p), ("alloc_size", C.c_size_t)]
 
@@ -98,7 +105,7 @@ SYMBOLS = [
     "dav1d_hip_lister_mask_offset", "dav1d_hip_lister_tables", "dav1d_hip_lister_block_warp", "dav1d_hip_lister_filter_sbrow",
     "dav1d_hip_surface_export", "dav1d_hip_surface_export_grain", "dav1d_hip_surface_export_scaled", "dav1d_hip_surface_scaled_rows_needed",
     "dav1d_hip_surface_export_rgb", "dav1d_hip_surface_rgb_rows_needed",
-    "dav1d_hip_surface_export_rgb_scaled", "dav1d_hip_surface_rgb_scaled_rows_needed", "dav1d_hip_surface_export_rgb_scaled_batch",
+    "dav1d_hip_surface_export_rgb_scaled", "dav1d_hip_surface_rgb_scaled_rows_needed", "dav1d_hip_surface_export_rgb_scaled_batch",    "dav1d_hip_colour_create", "dav1d_hip_colour_destroy", "dav1d_hip_surface_export_rgb_colour", "dav1d_hip_colour_tables",
 ]
 
 
@@ -303,6 +310,10 @@ def load(path=None):
         "dav1d_hip_surface_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), i]),
         "dav1d_hip_surface_export_rgb": (i, [vp, P(Surface), P(Picture), P(RgbParams), i, i]),
         "dav1d_hip_surface_rgb_rows_needed": (i, [P(Surface), P(Picture), P(RgbParams), i]),
+        "dav1d_hip_colour_create": (i, [vp, P(ColourDesc), P(vp)]),
+        "dav1d_hip_colour_destroy": (i, [vp, vp]),
+        "dav1d_hip_surface_export_rgb_colour": (i, [vp, P(Surface), P(Picture), P(RgbParams), vp, i, i]),
+        "dav1d_hip_colour_tables": (i, [i, i, i, i, i, C.c_float, C.c_float, vp, vp, P(i), vp, P(i)]),
         "dav1d_hip_surface_export_rgb_scaled": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
         "dav1d_hip_surface_export_rgb_scaled_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), P(i)]),
         "dav1d_hip_surface_rgb_scaled_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i]),

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import FilmGrainData  # noqa: F401
 from ._lib import ITX_TASK, MC_TASK, COMP_TASK, CDEF_TASK, LF_TASK, IPRED_TASK, LR_TASK, WARP_TASK, MC_SCALED_TASK, Picture, HostPicture  # noqa: F401  (re-exported)
 from ._lib import Surface as SurfaceDesc
-from ._lib import SurfaceRect, RgbParams
+from ._lib import SurfaceRect, RgbParams, ColourDesc, COLOUR_ENC_N
 
 LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
 SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR, SURFACE_RGB_PACKED, SURFACE_RGBA_PACKED = 0, 1, 2, 3, 4      # enum Dav1dHipSurfaceFormat
@@ -162,6 +162,14 @@ class DevicePicture:
         p = self._rgb_params(chroma_pos, scale, bias)
         _chk(self.ctx.lib.dav1d_hip_surface_export_rgb(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), C.byref(p), row0, row1), "surface_export_rgb")
 
+    def export_rgb_colour(self, surface, colour, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30):
+        """dav1d_hip_surface_export_rgb_colour: export_rgb followed in the same pass by the tables of `colour` (Context.colour / Context.colour_for):
+        linearise, 3x3 matrix, re-encode.  Float surfaces only (F32, F16); without `scale` / `bias` the sample is the tables' value itself (no 1 / max
+        factor).  rgb_rows_needed serves this call as it is.  Asynchronous like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_colour(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), C.byref(p), colour, row0, row1),
+             "surface_export_rgb_colour")
+
     def rgb_rows_needed(self, surface, chroma_pos, row1):
         """dav1d_hip_surface_rgb_rows_needed: the luma rows, from the top, that rows [0, row1) of export_rgb read"""
         p = self._rgb_params(chroma_pos, None, None)
@@ -267,8 +275,17 @@ class Surface:
         self.bufs = None
 
 
+def colour_tables(lib, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203.0, peak_nits=1000.0):
+    """dav1d_hip_colour_tables (host arithmetic, no device): lin (float32), m (3 x 3 float32), enc (uint16 bit patterns), has_matrix, has_enc"""
+    lin, m, enc = np.zeros(1 << bpc if bpc in (8, 10, 12) else 1, np.float32), np.zeros(9, np.float32), np.zeros(COLOUR_ENC_N, np.uint16)
+    has_matrix, has_enc = C.c_int(0), C.c_int(0)
+    _chk(lib.dav1d_hip_colour_tables(bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits, lin.ctypes.data, m.ctypes.data, C.byref(has_matrix),
+                                     enc.ctypes.data, C.byref(has_enc)), "colour_tables")
+    return lin, m.reshape(3, 3), enc, bool(has_matrix.value), bool(has_enc.value)
+
+
 def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0, crop=None, resize=False,
-                     chroma_pos=None, scale=None, bias=None):
+                     chroma_pos=None, scale=None, bias=None, colour=None):
     """Fills torch tensors on the picture's device through tensor.data_ptr(): `tensor` of shape (3, h, w) gets R, G, B planes; with
     `chroma` of shape (ceil(h / 2), 2 * ceil(w / 2)) given, `tensor` (h, w) gets luma and `chroma` the interleaved U, V of a 4:2:0
     picture (NV12 / P010 family).  The sample type follows the dtype (float32: F32; else `sample`, native by default).  The context should
@@ -277,8 +294,12 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     the rectangle that is scaled to it (DevicePicture.export_scaled; rows are then destination rows, and there is no grain).
     A tensor of shape (h, w, 3) or (h, w, 4) gets packed RGB / RGBA, and torch.float16 gets binary16 samples: both go through
     DevicePicture.export_rgb, as does any RGB tensor when `chroma_pos`, `scale` or `bias` is given (see there; no grain then).  With `resize=True`
-    these go through DevicePicture.export_rgb_scaled; the output size of a packed tensor is its shape[0] x shape[1] (a shape that reads both ways, (3, n, 3) or (3, n, 4), raises ValueError with these options)."""
+    these go through DevicePicture.export_rgb_scaled; the output size of a packed tensor is its shape[0] x shape[1] (a shape that reads both ways, (3, n, 3) or (3, n, 4), raises ValueError with these options).
+    `colour` (a handle of Context.colour / Context.colour_for): float RGB tensors go through DevicePicture.export_rgb_colour; not together with
+    `grain`, `crop` or `resize`."""
     import torch
+    if colour is not None and (grain is not None or crop is not None or resize):
+        raise ValueError("colour= goes through export_rgb_colour: no grain, no crop, no resize")
     if crop is not None and not resize:
         raise ValueError("crop= needs resize=True")
     if resize and grain is not None:
@@ -297,7 +318,7 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
         sample = SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_F16 if tensor.dtype == torch.float16 else SAMPLE_NATIVE
     es = tensor.element_size()
     packed = chroma is None and tensor.dim() == 3 and tuple(tensor.shape[:2]) == (h, w) and int(tensor.shape[2]) in (3, 4)
-    rgbx = packed or sample == SAMPLE_F16 or chroma_pos is not None or scale is not None or bias is not None
+    rgbx = packed or sample == SAMPLE_F16 or chroma_pos is not None or scale is not None or bias is not None or colour is not None
     if rgbx and (chroma is not None or grain is not None):
         raise ValueError("packed RGB, float16, chroma_pos, scale and bias go through export_rgb / export_rgb_scaled: RGB tensors only, no grain")
     if packed:
@@ -323,6 +344,9 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
     if rgbx and resize:
         pic.export_rgb_scaled(s, crop, chroma_pos or 0, scale, bias, row0, row1)
+        return s
+    if colour is not None:
+        pic.export_rgb_colour(s, colour, chroma_pos or 0, scale, bias, row0, row1)
         return s
     if rgbx:
         pic.export_rgb(s, chroma_pos or 0, scale, bias, row0, row1)
@@ -518,6 +542,37 @@ class Context:
 
     def last_kernel_ms(self):
         return float(self.lib.dav1d_hip_last_kernel_ms(self.h))
+
+    def colour(self, lin, matrix=None, enc=None, bpc=None):
+        """dav1d_hip_colour_create: a handle for DevicePicture.export_rgb_colour from tables of the caller — `lin`: 1 << bpc float32 values (code ->
+        linear); `matrix`: None or 9 values, row-major; `enc`: None or COLOUR_ENC_N binary16 bit patterns (uint16, or a float16 array), indexed by the
+        binary16 pattern of the clamped linear value.  Copies the tables to the device and waits.  colour_destroy() frees it."""
+        lin = np.ascontiguousarray(lin, dtype=np.float32)
+        if bpc is None:
+            bpc = int(lin.size).bit_length() - 1
+        if lin.size != 1 << bpc:
+            raise ValueError("lin has 1 << bpc entries")
+        d = ColourDesc(bpc=bpc, lin=lin.ctypes.data_as(C.POINTER(C.c_float)), has_matrix=int(matrix is not None))
+        if matrix is not None:
+            d.m[:] = [float(v) for v in np.asarray(matrix, dtype=np.float32).reshape(9)]
+        if enc is not None:
+            enc = np.ascontiguousarray(enc)
+            enc = np.ascontiguousarray(enc.view(np.uint16) if enc.dtype == np.float16 else enc, dtype=np.uint16)
+            if enc.size != COLOUR_ENC_N:
+                raise ValueError("enc has COLOUR_ENC_N entries")
+            d.enc = enc.ctypes.data_as(C.POINTER(C.c_uint16))
+        h = C.c_void_p()
+        _chk(self.lib.dav1d_hip_colour_create(self.h, C.byref(d), C.byref(h)), "colour_create")
+        return h
+
+    def colour_for(self, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203.0, peak_nits=1000.0):
+        """dav1d_hip_colour_tables, then colour(): the handle that takes pictures of AV1's transfer / primaries codes trc_in / pri_in to trc_out /
+        pri_out (8: linear light, 1.0 = white_nits)."""
+        lin, m, enc, has_matrix, has_enc = colour_tables(self.lib, bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits)
+        return self.colour(lin, m if has_matrix else None, enc if has_enc else None, bpc)
+
+    def colour_destroy(self, h):
+        _chk(self.lib.dav1d_hip_colour_destroy(self.h, h), "colour_destroy")
 
     def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None):
         """dav1d_hip_surface_export_rgb_scaled_batch: item k gets what pics[k].export_rgb_scaled(surfaces[k], crops[k], chroma_pos, scale, bias) writes,

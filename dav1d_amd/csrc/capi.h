@@ -41,6 +41,7 @@ struct Dav1dHipContext {
     int chunk_upload;           // 0: a frame's chunks go up as one transfer at frame end; 1: each chunk as it is submitted (DAV1D_HIP_CHUNK_UPLOAD)
     int recon_coop_below;       // paired kernels: launches of fewer groups than this take the cooperative form (recon.hip; DAV1D_HIP_RECON_COOP_BELOW)
     int post_bands;             // bands of the pipelined post filters, 0 = stage by stage (DAV1D_HIP_POST_BANDS)
+    int colour_cells;           // cells a wave of the colour-managed export takes, 0 (default) = cells_per_wave of surface_colour.hip (DAV1D_HIP_COLOUR_CELLS; a measuring and testing knob)
     int recon_pair_streams;     // side streams the paired launches of a recon list are dealt over (DAV1D_HIP_RECON_PAIR_STREAMS, 1 .. 3; default 2)
     int recon_pair_first;       // ... starting at side stream 1 .. 3 (DAV1D_HIP_RECON_PAIR_FIRST; default 2): which HARDWARE queue a stream shares with which other is a matter of the order the
                                 // streams were made in (the runtime deals them over GPU_MAX_HW_QUEUES = 4 queues), profiles/r06/hw_queues.txt

@@ -55,6 +55,7 @@ int dav1d_hip_open(Dav1dHipContext **out, int device, void *stream) {
     c->chunk_upload = (int) env_int("DAV1D_HIP_CHUNK_UPLOAD", 0);
     c->recon_coop_below = (int) env_int("DAV1D_HIP_RECON_COOP_BELOW", 4096);
     c->post_bands = (int) env_int("DAV1D_HIP_POST_BANDS", 0);
+    c->colour_cells = (int) env_int("DAV1D_HIP_COLOUR_CELLS", 0);
     c->ref_twin = (int) env_int("DAV1D_HIP_REF_TWIN", 1);
     c->recon_pair_streams = (int) env_int("DAV1D_HIP_RECON_PAIR_STREAMS", 2);
     // (per-context lists "a,b,...": the i-th context opened in the process takes element i mod length)
@@ -253,6 +254,7 @@ int dav1d_hip_set_option(Dav1dHipContext *c, const char *name, long value) {
     else if (!strcmp(name, "chunk_upload")) c->chunk_upload = (int) value;
     else if (!strcmp(name, "recon_coop_below")) c->recon_coop_below = (int) value;
     else if (!strcmp(name, "post_bands")) c->post_bands = (int) value;
+    else if (!strcmp(name, "colour_cells")) c->colour_cells = value < 0 ? 0 : value > 64 ? 64 : (int) value;
     else if (!strcmp(name, "ref_twin")) c->ref_twin = (int) value;
     else if (!strcmp(name, "recon_pair_streams")) c->recon_pair_streams = (int) value;
     else if (!strcmp(name, "recon_pair_first")) c->recon_pair_first = (int) std::max(1L, std::min(3L, (long) value));

@@ -112,6 +112,26 @@ __device__ __forceinline__ uint16_t f32_to_f16_bits(const float f) {
     return __builtin_bit_cast(uint16_t, (_Float16) f);
 #endif
 }
+// The float value of an IEEE binary16 pattern: exact, subnormals included (v_cvt_f32_f16); infinities and NaNs stay what they are.
+__device__ __forceinline__ float f16_bits_to_f32(const uint16_t h) {
+#ifdef DAV1D_HIP_EMU
+    const uint32_t sign = (uint32_t) (h & 0x8000u) << 16, e = (h >> 10) & 31, m = h & 0x3ffu;
+    uint32_t x;
+    if (e == 31) x = 0x7f800000u | m << 13;
+    else if (e) x = (e + 112) << 23 | m << 13;
+    else if (!m) x = 0;
+    else {                                                      // subnormal: m * 2^-24, normal in float32
+        const int top = 31 - __builtin_clz(m);                  // the leading one becomes the hidden bit
+        x = (uint32_t) (top + 103) << 23 | ((m << (23 - top)) & 0x7fffffu);
+    }
+    x |= sign;
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+#else
+    return (float) __builtin_bit_cast(_Float16, h);
+#endif
+}
 // v * s + b with a rounding after the product and one after the sum, never contracted into a fused multiply-add
 __device__ __forceinline__ float mul_add_2r(const float v, const float s, const float b) {
 #ifdef DAV1D_HIP_EMU

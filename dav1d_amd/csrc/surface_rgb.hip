@@ -19,174 +19,18 @@
 
 namespace {
 
-struct RgbxArgs {
-    RgbArgs r;
-    int ch;                 // rows of the chroma plane
-    int pos;                // chroma_pos
-    int hf, vf;             // taps across / down other than replication
-    int packed;             // samples a pixel in data[0] (3, 4), 0: planes
+// today's sample: one channel at a time, out(v, c)
+template <typename Out> struct PerChannel {
+    typedef typename Out::T T;
+    Out out; T alpha;
+    __device__ __forceinline__ void operator()(const int r, const int g, const int b, T &R, T &G, T &B) const { R = out(r, 0); G = out(g, 1); B = out(b, 2); }
 };
-
-// one sample of a plane (the same line request as the load8 around it)
-template <typename pixel, bool TILED>
-__device__ __forceinline__ uint32_t load1(const void *const base, const int stride, const int x, const int y)
-{
-    const pixel *const p = (const pixel *) base;
-    if (TILED) return p[(size_t) (y >> 3) * 8 * stride + (size_t) (x >> 3) * 64 + (y & 7) * 8 + (x & 7)];
-    return p[(size_t) y * stride + x];
-}
-
-template <typename pixel> __device__ __forceinline__ uint32_t pair_of(const Piece<8 * sizeof(pixel)> &u, const Piece<8 * sizeof(pixel)> &v, const int m) {
-    return (uint32_t) sample_of<pixel>(u, m) | (uint32_t) sample_of<pixel>(v, m) << 16;
-}
-template <typename piece_t> __device__ __forceinline__ piece_t piece_from_lane(const piece_t &p, const int lane) {
-    piece_t o;
-#pragma unroll
-    for (int k = 0; k < (int) (sizeof(piece_t) / 4); k++) o.a[k] = (uint32_t) __shfl((int) p.a[k], lane);
-    return o;
-}
-// the vertical taps of luma rows 2k (top) and 2k + 1 (bottom) on pairs of the rows above, at and below chroma row k, weights summing to 4
-__device__ __forceinline__ void taps_down(const int pos, const uint32_t up, const uint32_t own, const uint32_t dn, uint32_t &top, uint32_t &bot)
-{
-    if (pos == 1) { top = up + 3 * own; bot = 3 * own + dn; }
-    else { top = 4 * own; bot = 2 * (own + dn); }
-}
 
 template <typename pixel, bool TILED, int SSH, int SSV, typename Out>
 __global__ __launch_bounds__(64) void surface_rgbx_kernel(const RgbxArgs ax, const Out out)
 {
-    typedef typename Out::T T;
-    typedef Piece<8 * sizeof(pixel)> piece_t;
-    const RgbArgs &a = ax.r;
-    const int g = (int) blockIdx.x;
-    const int cyg = g / a.n_cx, cx = g - cyg * a.n_cx;
-    const int lane = threadIdx.x & 63, r = lane >> 3, c = lane & 7;
-    const int xc = cx * 64 + c * 8, yc = ((a.crow0 >> 3) + cyg) * 8 + r;
-    // (no lane leaves before the exchanges below: every lane of the wave takes part in them)
-    const bool active = xc < a.cw && yc >= a.crow0 && yc < a.crow1;
-    const int nloc = a.cw - xc;                      // chroma columns from this lane's first to the plane's end
-    const bool vf = SSV && ax.vf, hf = SSH && ax.hf;
-    piece_t u = piece_t(), v = piece_t(), yy[1 << SSV][1 << SSH];
-    if (active && !a.mono) {
-        u = load8<pixel, TILED>(a.s[1], a.sstride[1], xc, yc, nloc, a.swide[1]);
-        v = load8<pixel, TILED>(a.s[2], a.sstride[1], xc, yc, nloc, a.swide[1]);
-    }
-    // the rows above and below: the lanes above and below in the cell, a load at the cell's (the band's) first and last row, the row itself at the plane's
-    const bool edge_up = r == 0 || yc == a.crow0, edge_dn = r == 7 || yc == a.crow1 - 1;
-    piece_t uu = u, vu = v, ud = u, vd = v;
-    if (vf) {
-        uu = piece_from_lane(u, lane - 8); vu = piece_from_lane(v, lane - 8);
-        ud = piece_from_lane(u, lane + 8); vd = piece_from_lane(v, lane + 8);
-        if (active && edge_up) {
-            if (yc == 0) { uu = u; vu = v; }
-            else {
-                uu = load8<pixel, TILED>(a.s[1], a.sstride[1], xc, yc - 1, nloc, a.swide[1]);
-                vu = load8<pixel, TILED>(a.s[2], a.sstride[1], xc, yc - 1, nloc, a.swide[1]);
-            }
-        }
-        if (active && edge_dn) {
-            if (yc == ax.ch - 1) { ud = u; vd = v; }
-            else {
-                ud = load8<pixel, TILED>(a.s[1], a.sstride[1], xc, yc + 1, nloc, a.swide[1]);
-                vd = load8<pixel, TILED>(a.s[2], a.sstride[1], xc, yc + 1, nloc, a.swide[1]);
-            }
-        }
-    }
-    // the pair right of the lane's eight, rows above and below it likewise: the next lane's first, or (last lane of the cell's row) a load
-    const bool halo = active && hf && c == 7 && nloc > 8;
-    uint32_t h_own = 0, h_up = 0, h_dn = 0;
-    if (halo) h_own = load1<pixel, TILED>(a.s[1], a.sstride[1], xc + 8, yc) | load1<pixel, TILED>(a.s[2], a.sstride[1], xc + 8, yc) << 16;
-    if (hf && vf) {
-        h_up = (uint32_t) __shfl((int) h_own, lane - 8);
-        h_dn = (uint32_t) __shfl((int) h_own, lane + 8);
-        if (halo && edge_up) h_up = yc == 0 ? h_own : load1<pixel, TILED>(a.s[1], a.sstride[1], xc + 8, yc - 1) | load1<pixel, TILED>(a.s[2], a.sstride[1], xc + 8, yc - 1) << 16;
-        if (halo && edge_dn) h_dn = yc == ax.ch - 1 ? h_own : load1<pixel, TILED>(a.s[1], a.sstride[1], xc + 8, yc + 1) | load1<pixel, TILED>(a.s[2], a.sstride[1], xc + 8, yc + 1) << 16;
-    }
-    if (active) {
-#pragma unroll
-        for (int i = 0; i < 1 << SSV; i++)
-#pragma unroll
-            for (int j = 0; j < 1 << SSH; j++) {
-                const int x = (xc << SSH) + j * 8, y = (yc << SSV) + i;
-                if (x < a.w && y < a.row1) yy[i][j] = load8<pixel, TILED>(a.s[0], a.sstride[0], x, y, a.w - x, a.swide[0]);
-            }
-    }
-    // P[i][m]: the vertical taps (sum 4) of luma row i on chroma column m of the lane, U and V in the halves of a word; m = 8 is the neighbour
-    uint32_t P[1 << SSV][9];
-    const uint32_t grey = (uint32_t) a.mid * 0x10001u;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        const uint32_t own = a.mono ? grey : pair_of<pixel>(u, v, m);
-        if (vf) taps_down(ax.pos, pair_of<pixel>(uu, vu, m), own, pair_of<pixel>(ud, vd, m), P[0][m], P[SSV][m]);
-        else P[0][m] = P[SSV][m] = 4 * own;
-    }
-    if (hf) {
-        uint32_t hp[2];
-        if (vf) taps_down(ax.pos, h_up, h_own, h_dn, hp[0], hp[1]);
-        else hp[0] = hp[1] = 4 * h_own;
-#pragma unroll
-        for (int i = 0; i < 1 << SSV; i++) {
-            const uint32_t next = (uint32_t) __shfl((int) P[i][0], lane + 1);
-            P[i][8] = c == 7 ? hp[i] : next;
-#pragma unroll
-            for (int m = 1; m < 9; m++) P[i][m] = m < nloc ? P[i][m] : P[i][m - 1];       // right of the plane: its last column
-        }
-    }
-    if (!active) return;
-#pragma unroll
-    for (int j = 0; j < 1 << SSH; j++) {
-        const int x = (xc << SSH) + j * 8;
-        if (x >= a.w) continue;
-        int tr[8], tg[8], tb[8];
-#pragma unroll
-        for (int i = 0; i < 1 << SSV; i++) {
-            const int y = (yc << SSV) + i;
-            if (y >= a.row1) continue;
-            if (i == 0 || vf) {      // the chroma terms of the 8 samples of this unit (without taps down: the same for both rows of the lane)
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const int k = SSH ? j * 4 + (e >> 1) : e;
-                    uint32_t s = 2 * P[i][k];
-                    if (SSH && (e & 1) && hf) s = P[i][k] + P[i][k + 1];
-                    s = ((s + 0x00040004u) >> 3) & 0x1fff1fffu;
-                    const int cb = (int) (s & 0xffff) - a.mid, cr = (int) (s >> 16) - a.mid;
-                    if (a.identity) { tr[e] = cr + a.mid; tg[e] = 0; tb[e] = cb + a.mid; }
-                    else {
-                        tr[e] = dv::mad_i24(a.crv, cr, 8192);
-                        tg[e] = dv::mad_i24(-a.cgv, cr, dv::mad_i24(-a.cgu, cb, 8192));
-                        tb[e] = dv::mad_i24(a.cbu, cb, 8192);
-                    }
-                }
-            }
-            T R[8], G[8], B[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int Y = sample_of<pixel>(yy[i][j], e);
-                if (a.identity) { R[e] = out(tr[e], 0); G[e] = out(Y, 1); B[e] = out(tb[e], 2); continue; }
-                const int l = dv::mul_i24(a.cy, Y - a.yoff);
-                R[e] = out(dv::iclip((l + tr[e]) >> 14, 0, a.max), 0);
-                G[e] = out(dv::iclip((l + tg[e]) >> 14, 0, a.max), 1);
-                B[e] = out(dv::iclip((l + tb[e]) >> 14, 0, a.max), 2);
-            }
-            const int n = a.w - x;
-            if (ax.packed == 3) {
-                T t[24];
-#pragma unroll
-                for (int e = 0; e < 8; e++) { t[3 * e] = R[e]; t[3 * e + 1] = G[e]; t[3 * e + 2] = B[e]; }
-                store_packed<T, 24>((T *) ((uint8_t *) a.d[0] + (size_t) y * a.dstride[0]) + (size_t) x * 3, t, 3 * n, a.dwide);
-            } else if (ax.packed == 4) {
-                T t[32];
-#pragma unroll
-                for (int e = 0; e < 8; e++) { t[4 * e] = R[e]; t[4 * e + 1] = G[e]; t[4 * e + 2] = B[e]; t[4 * e + 3] = out.alpha; }
-                store_packed<T, 32>((T *) ((uint8_t *) a.d[0] + (size_t) y * a.dstride[0]) + (size_t) x * 4, t, 4 * n, a.dwide);
-            } else {
-                const size_t off = (size_t) x * sizeof(T);
-                store_run<T, 8>((T *) ((uint8_t *) a.d[0] + (size_t) y * a.dstride[0] + off), R, n, a.dwide);
-                store_run<T, 8>((T *) ((uint8_t *) a.d[1] + (size_t) y * a.dstride[1] + off), G, n, a.dwide);
-                store_run<T, 8>((T *) ((uint8_t *) a.d[2] + (size_t) y * a.dstride[2] + off), B, n, a.dwide);
-            }
-        }
-    }
+    const PerChannel<Out> fn = { out, out.alpha };
+    rgbx_cell<pixel, TILED, SSH, SSV>(ax, (int) blockIdx.x, fn);
 }
 
 template <typename pixel, bool TILED, typename Out>
@@ -195,17 +39,8 @@ int launch_rgbx(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, cons
 {
     typedef typename Out::T T;
     unsigned n_cells;
-    RgbxArgs ax = RgbxArgs();
-    ax.r = make_rgb_args<pixel, TILED, T>(dst, src, planes, row0, row1, &n_cells);
+    const RgbxArgs ax = make_rgbx_args<pixel, TILED, T>(dst, src, planes, p, row0, row1, &n_cells);
     const SurfaceGeom g = surface_geom(src, row0, row1);
-    ax.ch = g.ch; ax.pos = p.chroma_pos;
-    ax.hf = g.ss_hor && p.chroma_pos; ax.vf = g.ss_ver && p.chroma_pos;
-    ax.packed = dst->format == DAV1D_HIP_SURFACE_RGB_PACKED ? 3 : dst->format == DAV1D_HIP_SURFACE_RGBA_PACKED ? 4 : 0;
-    if (ax.packed) {          // one plane; a lane's run starts at a multiple of its size, so the chunk's alignment of base and stride decides
-        const int run = 8 * ax.packed * (int) sizeof(T);
-        ax.r.dwide = aligned_to(dst->data[0], dst->stride[0], run % 16 ? 8 : 16);
-        ax.r.d[1] = ax.r.d[2] = nullptr;
-    }
     const dim3 grid(n_cells);
     hipStream_t st = c->stream;
     if (g.ss_ver) hipLaunchKernelGGL((surface_rgbx_kernel<pixel, TILED, 1, 1, Out>), grid, dim3(64), 0, st, ax, out);

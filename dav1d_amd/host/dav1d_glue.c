@@ -73,6 +73,11 @@ typedef struct Hip {
     int (*surface_export_rgb)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipRgbParams *, int, int);
     int (*surface_export_rgb_scaled)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipSurfaceRect *, const Dav1dHipRgbParams *,
                                      int, int);
+    int (*colour_tables)(int, int, int, int, int, float, float, float *, float *, int *, uint16_t *, int *);
+    int (*colour_create)(Dav1dHipContext *, const Dav1dHipColourDesc *, Dav1dHipColour **);
+    int (*colour_destroy)(Dav1dHipContext *, Dav1dHipColour *);
+    int (*surface_export_rgb_colour)(Dav1dHipContext *, const Dav1dHipSurface *, const Dav1dHipPicture *, const Dav1dHipRgbParams *, const Dav1dHipColour *,
+                                     int, int);
     int (*frame_set_progress_callback)(Dav1dHipFrame *, void (*)(void *, int, const Dav1dHipPicture *), void *);
     int (*live_objects)(long long *);
     int (*device_count)(void);
@@ -113,6 +118,9 @@ typedef struct Dev {
     int have_threads;
     void *targ[3][3];
     atomic_int n_frames, n_peer_copies, n_band_copies, n_twin_only;
+    /* the colour handle of dav1d_hip_glue_output_rgb_colour on ctx_out and what it was made for: rebuilt when a stream's codes or peak change */
+    Dav1dHipColour *colour;
+    struct ColourKey { int bpc, trc_in, pri_in, trc_out, pri_out; float white, peak; } colour_key;
 } Dev;
 
 /* a frame ends badly because a frame it predicts from did: dav1d's error (DAV1D_ERR(EINVAL), as check_tile makes it), not the backend's */
@@ -135,6 +143,7 @@ struct Dav1dHipGlue {
     Dav1dHipGluePicture *free_pics[32];
     int n_free_pics, closing;
     pthread_mutex_t pic_mtx;
+    pthread_mutex_t colour_mtx;      /* the cached colour handles: a handle serves one call at a time */
     atomic_int n_row_publications, n_backend_failures;
 };
 
@@ -773,6 +782,70 @@ int dav1d_hip_glue_output_rgb_scaled(Dav1dHipGlue *const g, const Dav1dPicture *
     return !rc ? 0 : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
 }
 
+/* Colour-managed RGB (dav1d_hip_surface_export_rgb_colour): the picture's samples taken from the transfer and primaries its sequence header names
+ * (DAV1D_TRC_UNKNOWN / DAV1D_COLOR_PRI_UNKNOWN count as BT.709) to trc_out / pri_out, with the tables of dav1d_hip_colour_tables.  peak_nits is the
+ * content light level's max_content_light_level where the picture carries one that is not zero, else 1000 for PQ and HLG, else white_nits.  One handle
+ * per device is kept between calls and rebuilt when (bpc, codes, white, peak) change.  `params` NULL as in dav1d_hip_glue_output_rgb.  Film grain, when
+ * the frame header carries any, goes the two-pass route of that function.  Float surfaces only.  Returns when the surface is written.  The library
+ * calls behind it are tested at the C ABI (tests/test_surface_colour.py mirrors the call sequence). */
+int dav1d_hip_glue_output_rgb_colour(Dav1dHipGlue *const g, const Dav1dPicture *const pic, const Dav1dHipSurface *const dst, const Dav1dHipRgbParams *const params,
+                                     const int trc_out, const int pri_out, const float white_nits) {
+    if (!g || !pic || !pic->allocator_data || !dst) return DAV1D_ERR(EINVAL);
+    const Dav1dHipGluePicture *const hp = pic->allocator_data;
+    const Dav1dFilmGrainData *const fg = &pic->frame_hdr->film_grain.data;
+    const int grain_here = fg->num_y_points || fg->num_uv_points[0] || fg->num_uv_points[1] || (fg->clip_to_restricted_range && fg->chroma_scaling_from_luma);
+    Dav1dHipRgbParams p;
+    memset(&p, 0, sizeof(p));
+    if (params) p = *params;
+    else p.chroma_pos = pic->seq_hdr->chr == DAV1D_CHR_COLOCATED ? 2 : 1;
+    const int trc_in = pic->seq_hdr->trc == DAV1D_TRC_UNKNOWN ? DAV1D_TRC_BT709 : (int) pic->seq_hdr->trc;
+    const int pri_in = pic->seq_hdr->pri == DAV1D_COLOR_PRI_UNKNOWN ? DAV1D_COLOR_PRI_BT709 : (int) pic->seq_hdr->pri;
+    const int hdr = trc_in == DAV1D_TRC_SMPTE2084 || trc_in == DAV1D_TRC_HLG;
+    const float peak = pic->content_light && pic->content_light->max_content_light_level ? (float) pic->content_light->max_content_light_level :
+                       hdr ? 1000.0f : white_nits;
+    const struct ColourKey key = { pic->p.bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak < white_nits ? white_nits : peak };
+    Dev *const dv = &g->dev[hp->ref_dev];
+    Dav1dHipContext *const ctx_out = dv->ctx_out;
+    Dav1dHipGrain *grain = NULL;
+    Dav1dHipPicture tmp;
+    memset(&tmp, 0, sizeof(tmp));
+    const int thread_dev = borrow_thread(g, ctx_out);
+    pthread_mutex_lock(&g->colour_mtx);
+    int rc = 0, no_mem = 0, bad_args = 0;
+    if (!dv->colour || memcmp(&dv->colour_key, &key, sizeof(key))) {
+        if (dv->colour) { g->hip.colour_destroy(ctx_out, dv->colour); dv->colour = NULL; }
+        Dav1dHipColourDesc d;
+        memset(&d, 0, sizeof(d));
+        float *const lin = malloc(((size_t) 1 << 12) * sizeof(*lin));
+        uint16_t *const enc = malloc(DAV1D_HIP_COLOUR_ENC_N * sizeof(*enc));
+        int has_enc = 0;
+        if (!lin || !enc) rc = -ENOMEM;
+        if (!rc) rc = g->hip.colour_tables(key.bpc, trc_in, pri_in, trc_out, pri_out, key.white, key.peak, lin, d.m, &d.has_matrix, enc, &has_enc);
+        bad_args = rc == -EINVAL || rc == -ENOTSUP;
+        d.bpc = key.bpc; d.lin = lin; d.enc = has_enc ? enc : NULL;
+        if (!rc) rc = g->hip.colour_create(ctx_out, &d, &dv->colour);
+        if (!rc) dv->colour_key = key;
+        free(lin); free(enc);
+    }
+    no_mem = rc == -ENOMEM;
+    if (!rc && grain_here) {
+        rc = g->hip.fg_prepare(ctx_out, &grain, (const Dav1dHipFilmGrainData *) fg, pic->p.bpc, pic->p.layout);
+        if (!rc) rc = g->hip.picture_alloc(ctx_out, &tmp, pic->p.w, pic->p.h, pic->p.layout, pic->p.bpc);
+        no_mem = rc == -ENOMEM;
+        if (!rc) rc = g->hip.fg_apply_prepared(ctx_out, &tmp, &hp->ref, grain, pic->seq_hdr->mtrx == DAV1D_MC_IDENTITY);
+    }
+    if (!rc) {
+        rc = g->hip.surface_export_rgb_colour(ctx_out, dst, grain_here ? &tmp : &hp->ref, &p, dv->colour, 0, pic->p.h);
+        bad_args = rc == -EINVAL || rc == -ENOTSUP;
+    }
+    if (!rc) rc = g->hip.sync(ctx_out);
+    if (tmp.alloc) g->hip.picture_free(ctx_out, &tmp);
+    if (grain) g->hip.fg_grain_destroy(ctx_out, grain);
+    pthread_mutex_unlock(&g->colour_mtx);
+    return_thread(g, thread_dev);
+    return !rc ? 0 : no_mem ? DAV1D_ERR(ENOMEM) : bad_args ? DAV1D_ERR(EINVAL) : DAV1D_ERR(EIO);
+}
+
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *const g) { return g ? atomic_load(&g->n_backend_failures) : 0; }
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *const g) { return g ? atomic_load(&g->n_row_publications) : 0; }
 int dav1d_hip_glue_devices(const Dav1dHipGlue *const g) { return g ? g->n_dev : 0; }
@@ -797,6 +870,7 @@ int dav1d_hip_glue_create(Dav1dHipGlue **const out, const Dav1dHipGlueOptions *c
     g->o = *o;
     pthread_mutex_init(&g->q_mtx, NULL);
     pthread_mutex_init(&g->pic_mtx, NULL);
+    pthread_mutex_init(&g->colour_mtx, NULL);
     pthread_cond_init(&g->q_cond, NULL);
     g->hip.dl = dlopen(o->hip_lib, RTLD_NOW | RTLD_LOCAL);
     if (!g->hip.dl) goto fail;
@@ -812,7 +886,9 @@ int dav1d_hip_glue_create(Dav1dHipGlue **const out, const Dav1dHipGlueOptions *c
     SYM(fg_apply, "dav1d_hip_fg_apply"); SYM(picture_alloc, "dav1d_hip_picture_alloc"); SYM(picture_free, "dav1d_hip_picture_free");
     SYM(plane_download, "dav1d_hip_plane_download"); SYM(surface_export, "dav1d_hip_surface_export"); SYM(surface_export_grain, "dav1d_hip_surface_export_grain");
     SYM(fg_prepare, "dav1d_hip_fg_prepare"); SYM(fg_grain_destroy, "dav1d_hip_fg_grain_destroy"); SYM(fg_apply_prepared, "dav1d_hip_fg_apply_prepared");
-    SYM(surface_export_rgb, "dav1d_hip_surface_export_rgb"); SYM(surface_export_rgb_scaled, "dav1d_hip_surface_export_rgb_scaled"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
+    SYM(surface_export_rgb, "dav1d_hip_surface_export_rgb"); SYM(colour_tables, "dav1d_hip_colour_tables"); SYM(colour_create, "dav1d_hip_colour_create");
+    SYM(colour_destroy, "dav1d_hip_colour_destroy"); SYM(surface_export_rgb_colour, "dav1d_hip_surface_export_rgb_colour");
+    SYM(surface_export_rgb_scaled, "dav1d_hip_surface_export_rgb_scaled"); SYM(frame_set_progress_callback, "dav1d_hip_frame_set_progress_callback");
     SYM(live_objects, "dav1d_hip_live_objects"); SYM(device_count, "dav1d_hip_device_count"); SYM(use, "dav1d_hip_context_use");
     SYM(enable_peer_access, "dav1d_hip_enable_peer_access"); SYM(current_device, "dav1d_hip_current_device"); SYM(set_device, "dav1d_hip_set_device");
     SYM(picture_copy_peer, "dav1d_hip_picture_copy_peer"); SYM(picture_copy_peer_rows, "dav1d_hip_picture_copy_peer_rows"); SYM(picture_retile, "dav1d_hip_picture_retile");
@@ -914,6 +990,7 @@ void dav1d_hip_glue_destroy(Dav1dHipGlue *const g) {
         free(g->fcs);
     }
     for (int d = 0; d < DAV1D_HIP_GLUE_MAX_DEVICES; d++) {
+        if (g->dev[d].colour) g->hip.colour_destroy(g->dev[d].ctx_out, g->dev[d].colour);
         if (g->dev[d].ctx_peer) g->hip.close(g->dev[d].ctx_peer);
         if (g->dev[d].ctx_out) g->hip.close(g->dev[d].ctx_out);
         if (g->dev[d].ctx_up) g->hip.close(g->dev[d].ctx_up);
@@ -923,6 +1000,7 @@ void dav1d_hip_glue_destroy(Dav1dHipGlue *const g) {
     if (g->hip.dl) dlclose(g->hip.dl);
     pthread_mutex_destroy(&g->q_mtx);
     pthread_mutex_destroy(&g->pic_mtx);
+    pthread_mutex_destroy(&g->colour_mtx);
     pthread_cond_destroy(&g->q_cond);
     if (g_glue == g) g_glue = NULL;
     free(g);

@@ -110,6 +110,12 @@ int dav1d_hip_glue_output_rgb(Dav1dHipGlue *g, const Dav1dPicture *pic, const Da
  * chroma upsampled at its site, in one pass.  `params` NULL as above.  No film grain.  Returns when the surface is written. */
 int dav1d_hip_glue_output_rgb_scaled(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, const Dav1dHipSurfaceRect *crop,
                                      const Dav1dHipRgbParams *params);
+/* ---- ... and colour-managed (dav1d_hip_surface_export_rgb_colour): linearised from pic->seq_hdr->trc, taken from pic->seq_hdr->pri to pri_out, re-encoded
+ * with trc_out (8: linear light, 1.0 = white_nits), H.273 codes as dav1d_hip_colour_tables knows them; unknown codes of the stream count as BT.709.
+ * peak_nits: pic->content_light->max_content_light_level if present and not zero, else 1000 for PQ / HLG, else white_nits.  dst->sample is F32 or F16.
+ * The film grain of the frame header, if any, is applied (two passes, as above).  Returns when the surface is written. */
+int dav1d_hip_glue_output_rgb_colour(Dav1dHipGlue *g, const Dav1dPicture *pic, const Dav1dHipSurface *dst, const Dav1dHipRgbParams *params,
+                                     int trc_out, int pri_out, float white_nits);
 
 int dav1d_hip_glue_backend_failures(const Dav1dHipGlue *g);    /* frames that failed INSIDE the backend (not: frames dav1d rejects) */
 int dav1d_hip_glue_row_publications(const Dav1dHipGlue *g);

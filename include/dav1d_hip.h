@@ -80,7 +80,9 @@ DAV1D_HIP_API void dav1d_hip_graph_destroy(Dav1dHipContext *c, Dav1dHipGraph *g)
  * "prep_async": 1 (default) = the chunk preparation of a tile-sbrow the lister hands in runs on threads of the library for frames of at most 8 tiles (the
  * listing thread goes on with the tile's next row; errors surface at dav1d_hip_frame_end), 2 = for every frame, 0 = on the submitting thread;
  * "chunk_order": 1 = the prepared lists of a tile-sbrow are ordered for the device — by code path and reference, a few per cent on the
- * launches for a tenth more host time per frame; 0, the default, leaves decode order); -EINVAL for an unknown name. */
+ * launches for a tenth more host time per frame; 0, the default, leaves decode order;
+ * "colour_cells": the cells (1 .. 64) a wave of dav1d_hip_surface_export_rgb_colour takes in its loop, 0, the default, = the library's choice from the
+ * picture's size — the bytes written do not depend on it); -EINVAL for an unknown name. */
 DAV1D_HIP_API int dav1d_hip_set_option(Dav1dHipContext *c, const char *name, long value);
 /* Reads back what a context counts or was set to: "intra_sb_fallbacks" = frames of this context whose one-launch intra pass had workgroups give
  * up waiting for a neighbour and was finished by launches per level (0 in a sound run: the one-launch form rests on workgroups being dispatched
@@ -367,6 +369,58 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_scaled_batch(Dav1dHipContext *c, 
                                                             const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
                                                             const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */,
                                                             int *bad_item /* may be NULL */);
+/* Colour-managed RGB (dav1d_amd/csrc/surface_colour.hip): dav1d_hip_surface_export_rgb followed, in the same pass, by the stage
+ * every colour pipeline has — a 1-D table, a 3x3 matrix, a 1-D table ("degamma, CSC, regamma") — with tables of the caller.
+ * Definition.  Let (R, G, B) be the integers in [0, max] that dav1d_hip_surface_export_rgb computes for a pixel (the same matrix, range, sited chroma,
+ * I400 rule and matrix-0 rule).  In float32, every operation rounded on its own, NO product ever fused into a sum:
+ *   1. l_c = lin[code_c], c = R, G, B.
+ *   2. with has_matrix: p_ij = m[3 i + j] * l_j, o_i = (p_i0 + p_i1) + p_i2; else o = l.
+ *   3. with enc: x = o > 0 ? (o < 1 ? o : 1) : 0 (negative values, -0.0 and NaN give +0); h = the binary16 bit pattern of x (ties to even,
+ *      subnormals kept: 0 <= h <= 0x3C00); f = the float32 value of the binary16 enc[h].  Without enc: f = o.
+ *   4. dst->sample is F32 or F16 only.  Without normalisation the sample is f — there is NO 1 / max factor, the tables define the unit; with
+ *      params->normalize it is f * scale[c] + bias[c] under the two roundings of dav1d_hip_surface_export_rgb.  F16 stores the binary16 nearest to
+ *      that (ties to even, subnormals kept, overflow to infinity); alpha is 1.0.  Formats RGB_PLANAR, RGB_PACKED, RGBA_PACKED.
+ * Results whose intermediates (a product, a sum, a table entry) are float32 denormals are IEEE on the device this was measured on and otherwise not pinned.
+ * The binary16 index keeps an sRGB -> linear -> sRGB round trip exact at 8 and 10 bits: floor(enc[f16(lin[v])] * max + 0.5) == v for every code v
+ * with the tables of dav1d_hip_colour_tables; at 12 bits up to one code of error appears (binary16 has 11 significant bits).
+ * Rows [row0, row1) and bands exactly as in dav1d_hip_surface_export_rgb; dav1d_hip_surface_rgb_rows_needed serves this call unchanged.
+ * dav1d_hip_colour_create copies the tables to memory of the context's device and may wait for the device (a call per stream, not per frame).  The
+ * handle lives until dav1d_hip_colour_destroy (which waits for the context's stream) and, like the grain handle, serves one context at a time.
+ * The export is asynchronous exactly like dav1d_hip_surface_export_rgb: one launch on the context's stream, dav1d_hip_last_kernel_ms reports its device
+ * time, no allocation, no host wait, `src` is const and a DAV1D_HIP_TWIN_ONLY picture stays one, nothing written outside the visible samples of the
+ * rows asked for.
+ * Errors, before anything is enqueued: everything dav1d_hip_surface_export_rgb refuses, with its code; -EINVAL for a NULL colour, an integer sample
+ * (NATIVE, MSB16), a handle whose bpc is not the picture's; -EXDEV for a handle of another device.  dav1d_hip_colour_create: -EINVAL for a NULL
+ * argument, a NULL lin, a bpc other than 8, 10, 12, a lin or (with has_matrix) m entry that is not finite, an enc entry with all exponent bits set;
+ * -ENOMEM. */
+#define DAV1D_HIP_COLOUR_ENC_N 15361   /* binary16 patterns 0x0000 .. 0x3C00: every half in [0, 1] */
+typedef struct Dav1dHipColourDesc {
+    int bpc;               /* 8, 10, 12: lin has 1 << bpc entries */
+    const float *lin;      /* required: code value -> linear value */
+    int has_matrix;
+    float m[9];            /* row-major, o = m * l */
+    const uint16_t *enc;   /* NULL: none; else DAV1D_HIP_COLOUR_ENC_N binary16 bit patterns */
+} Dav1dHipColourDesc;
+typedef struct Dav1dHipColour Dav1dHipColour;
+DAV1D_HIP_API int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourDesc *d, Dav1dHipColour **out);
+DAV1D_HIP_API int dav1d_hip_colour_destroy(Dav1dHipContext *c, Dav1dHipColour *h);
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                      const Dav1dHipRgbParams *params /* NULL = all zero */, const Dav1dHipColour *colour,
+                                                      int row0, int row1);
+/* Host arithmetic that fills a Dav1dHipColourDesc from AV1's (H.273) codes: computed in double, rounded once to the table's type, no device involved.
+ * lin[v] is the light of code v: the inverse OETF / EOTF of trc_in at v / max — 1, 6, 14, 15: the BT.709 curve; 13: sRGB; 4: gamma 2.2; 8: linear;
+ * 16: PQ (ST 2084, absolute, 10000 nits at v = max); 18: HLG, the inverse OETF only, scaled so that v = max is peak_nits (NO OOTF: scene light is
+ * shown as display light, a limitation).  SDR transfers give light relative to white_nits (v = max is white_nits).
+ * The unit: with trc_out == 8 (linear out) 1.0 means white_nits and there is no enc (*has_enc = 0, enc untouched; HDR light exceeds 1.0).  Otherwise
+ * 1.0 means peak_nits, and enc[h] = f16(OETF_out(tone(x p))), x the value of half h, p = peak_nits / white_nits, tone(y) = y (1 + y / p^2) / (1 + y)
+ * (the identity at p == 1; maps p to 1), applied PER CHANNEL (hues of saturated highlights shift; a luminance-based operator is not built).
+ * trc_out: 8, 13, 1 / 6 / 14 / 15, 4.  Primaries 1 (BT.709), 9 (BT.2020), 12 (P3-D65): m = RGB -> XYZ -> RGB from the H.273 chromaticities (all three
+ * share D65: no adaptation); equal primaries give *has_matrix = 0 and the identity in m.
+ * -ENOTSUP for any other code; -EINVAL for a NULL pointer, a bpc other than 8, 10, 12, white_nits <= 0 or peak_nits < white_nits (or not finite).
+ * A caller with a curve of its own bypasses this helper and hands dav1d_hip_colour_create its own tables. */
+DAV1D_HIP_API int dav1d_hip_colour_tables(int bpc, int trc_in, int pri_in, int trc_out, int pri_out, float white_nits, float peak_nits,
+                                          float *lin /* [1 << bpc] */, float m[9], int *has_matrix,
+                                          uint16_t *enc /* [DAV1D_HIP_COLOUR_ENC_N] */, int *has_enc);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -25,6 +25,10 @@ one pair of events around the N calls, in the same run on the same pictures and 
 once.  (a) N = 8 and N = 32 distinct pictures, the 1792 x 1792 centre crop to 224 x 224; (b) N = 32 crops of ONE picture, tiled over the frame, to 224 x 224;
 (c) N = 8 pictures at 4:1; (d) one 4:1 item and 31 of the 224 x 224 items.  (a) to (c) as packed RGBA float16 normalised at chroma_pos 1 and as planar
 float16 at chroma_pos 0.  The 32 pictures share one host image (their device memory is their own): the time does not depend on the pixels.
+--colour: dav1d_hip_surface_export_rgb_colour with the tables of PQ / BT.2020 -> sRGB / BT.709 (dav1d_hip_colour_tables, 203 / 1000 nits) — (a) lin only,
+planar float16; (b) lin + matrix, planar float16; (c) lin + matrix + enc, packed RGBA float16 normalised, chroma_pos 1 — each against
+dav1d_hip_surface_export_rgb to the same format and sample with the same parameters, in the same run on the same pictures: the new call moves the
+yardstick's bytes and adds three to six table reads a pixel.  --cells 1,2,4: (a) and (c) again with the context option colour_cells set (the cells a wave takes).
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -325,6 +329,75 @@ def rgb_scaled_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def colour_runs(a, ctx, ev, pics, src_bytes):
+    """the colour-managed export against export_rgb to the same format and sample"""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    mx = (1 << bpc) - 1
+    scale, bias = [1.0 / s for s in (0.229, 0.224, 0.225)], [-m / s for m, s in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))]
+    yscale = [v / mx for v in scale]          # the yardstick's samples are v / max
+    lin, m, enc, has_matrix, has_enc = api.colour_tables(ctx.lib, bpc, 16, 9, 13, 1, 203.0, 1000.0)
+    assert has_matrix and has_enc
+    handles = {"lin": ctx.colour(lin, bpc=bpc), "lin + matrix": ctx.colour(lin, m, bpc=bpc), "lin + matrix + enc": ctx.colour(lin, m, enc, bpc=bpc)}
+    P, K4 = api.SURFACE_RGB_PLANAR, api.SURFACE_RGBA_PACKED
+    planar = [ctx.surface(w, h, layout, bpc, P, api.SAMPLE_F16, matrix=9) for _ in range(a.pairs)]
+    packed = [ctx.surface(w, h, layout, bpc, K4, api.SAMPLE_F16, matrix=9) for _ in range(a.pairs)]
+    runs = []
+
+    def add(name, surfs, n, pos, sc, bi, handle, yard, cells=0, ysc=None):
+        if handle is None:
+            def call(k):
+                pics[k % a.pairs].export_rgb(surfs[k % a.pairs], pos, ysc, bi)
+        else:
+            def call(k):
+                pics[k % a.pairs].export_rgb_colour(surfs[k % a.pairs], handle, pos, sc, bi)
+        runs.append((name, src_bytes + n * 2 * w * h, call, yard, cells))
+        return name
+    y_p = add("export_rgb: planar float16, chroma_pos 1 (yardstick)", planar, 3, 1, None, None, None, None)
+    add("(a) export_rgb_colour lin: planar float16, chroma_pos 1", planar, 3, 1, None, None, handles["lin"], y_p)
+    add("(b) export_rgb_colour lin + matrix: planar float16, chroma_pos 1", planar, 3, 1, None, None, handles["lin + matrix"], y_p)
+    y_k = add("export_rgb: packed RGBA float16 normalised, chroma_pos 1 (yardstick)", packed, 4, 1, None, bias, None, None, ysc=yscale)
+    add("(c) export_rgb_colour lin + matrix + enc: packed RGBA float16 normalised, chroma_pos 1", packed, 4, 1, scale, bias, handles["lin + matrix + enc"], y_k)
+    for cells in a.cells:
+        add("(a) with colour_cells %d" % cells, planar, 3, 1, None, None, handles["lin"], y_p, cells)
+        add("(c) with colour_cells %d" % cells, packed, 4, 1, scale, bias, handles["lin + matrix + enc"], y_k, cells)
+    print("# surface_bench --colour on %s: %dx%d 4:2:0 %d-bit twin-only sources, %d picture / surface pairs in rotation, 20 warm-up + %d timed calls per variant, %d repeats"
+          % (socket.gethostname(), w, h, bpc, a.pairs, a.calls, a.repeats))
+    print("# tables: PQ / BT.2020 -> sRGB / BT.709, white 203 nits, peak 1000 nits; bytes per call = bytes read + bytes written, from the shapes (tables not counted)")
+    results = {r[0]: [] for r in runs}
+    for rep in range(a.repeats):
+        for name, nbytes, call, _, cells in runs:
+            ctx.set_option("colour_cells", cells)
+            for k in range(20):
+                call(k)
+            ctx.sync()
+            ev.start()
+            for k in range(a.calls):
+                call(k)
+            ms = ev.stop_ms() / a.calls
+            results[name].append(ms)
+            print("repeat %d  %-90s %8.4f ms/call  %7.1f MB/call  %7.0f GB/s" % (rep, name, ms, nbytes / 1e6, nbytes / ms / 1e6))
+    ctx.set_option("colour_cells", 0)
+    print("# summary (min / median / max ms per call over the repeats)")
+    for name, nbytes, _, _, _ in runs:
+        v = sorted(results[name])
+        print("summary   %-90s %8.4f / %8.4f / %8.4f ms   median %7.0f GB/s" % (name, v[0], v[len(v) // 2], v[-1], nbytes / v[len(v) // 2] / 1e6))
+    for name, _, _, yard, _ in runs:
+        if yard is None:
+            continue
+        v, u = sorted(results[name]), sorted(results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-90s median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms (min %.4f - max %.4f): %s (ratio %.3f)"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], u[0], u[-1], "met" if ok else "NOT met", v[len(v) // 2] / u[len(u) // 2]))
+    ctx.sync()
+    for hd in handles.values():
+        ctx.colour_destroy(hd)
+    for s in planar + packed:
+        s.free()
+    for p in pics:
+        p.free()
+    ctx.close()
+
+
 def batch_runs(a, ctx, ev, pics):
     """one batch call against the N single calls it replaces, per variant and output"""
     from dav1d_amd._lib import Picture, RgbParams, Surface as SurfaceDesc
@@ -413,6 +486,8 @@ def main():
     ap.add_argument("--rgb", action="store_true", help="dav1d_hip_surface_export_rgb (sited chroma, packed, float16) against the plain export to RGB planes")
     ap.add_argument("--rgb-scaled", action="store_true", help="dav1d_hip_surface_export_rgb_scaled against export_scaled into a picture + export_rgb from it")
     ap.add_argument("--batch", action="store_true", help="dav1d_hip_surface_export_rgb_scaled_batch against the N single calls it replaces")
+    ap.add_argument("--colour", action="store_true", help="dav1d_hip_surface_export_rgb_colour (PQ / BT.2020 -> sRGB / BT.709) against export_rgb to the same format")
+    ap.add_argument("--cells", type=lambda v: [int(x) for x in v.split(",") if x], default=[], help="--colour: variants (a) and (c) again with these values of the option colour_cells")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
@@ -454,6 +529,8 @@ def main():
         return rgb_scaled_runs(a, ctx, ev, pics, src_bytes)
     if a.batch:
         return batch_runs(a, ctx, ev, pics)
+    if a.colour:
+        return colour_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
