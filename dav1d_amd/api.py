@@ -17,6 +17,14 @@ LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
 SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR, SURFACE_RGB_PACKED, SURFACE_RGBA_PACKED = 0, 1, 2, 3, 4      # enum Dav1dHipSurfaceFormat
 SAMPLE_NATIVE, SAMPLE_MSB16, SAMPLE_F32, SAMPLE_F16 = 0, 1, 2, 3      # enum Dav1dHipSurfaceSample
 CHROMA_REPLICATE, CHROMA_VERTICAL, CHROMA_COLOCATED = 0, 1, 2         # Dav1dHipRgbParams.chroma_pos
+RESIZE_BILINEAR = 0                                                   # enum Dav1dHipResizeFilter
+_INTERP = {"bilinear": RESIZE_BILINEAR}                               # export_to_tensor / export_batch_to_tensor: interp=
+
+
+def _filter_of(interp):
+    if interp not in _INTERP:
+        raise ValueError("interp= is None or one of %s" % sorted(_INTERP))
+    return _INTERP[interp]
 
 
 class HipError(RuntimeError):
@@ -192,6 +200,21 @@ class DevicePicture:
         _chk(min(n, 0), "surface_rgb_scaled_rows_needed")
         return n
 
+    def export_rgb_resized(self, surface, crop=None, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_resized: export_rgb_scaled to ANY size — an axis of the rectangle `crop` that is shorter than the surface's
+        is interpolated up (RESIZE_BILINEAR: linear, half-sample centres), one that is longer goes down through the area scaler as before, every
+        plane and axis on its own.  Everything else as in export_rgb_scaled.  Asynchronous like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_resized(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), int(filter),
+                                                               row0, row1), "surface_export_rgb_resized")
+
+    def rgb_resized_rows_needed(self, surface, crop, chroma_pos, row1, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_rgb_resized_rows_needed: the source luma rows, from the top, that destination rows [0, row1) of export_rgb_resized read"""
+        p = self._rgb_params(chroma_pos, None, None)
+        n = self.ctx.lib.dav1d_hip_surface_rgb_resized_rows_needed(C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), int(filter), row1)
+        _chk(min(n, 0), "surface_rgb_resized_rows_needed")
+        return n
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -285,7 +308,7 @@ def colour_tables(lib, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203
 
 
 def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0, crop=None, resize=False,
-                     chroma_pos=None, scale=None, bias=None, colour=None):
+                     chroma_pos=None, scale=None, bias=None, colour=None, interp=None):
     """Fills torch tensors on the picture's device through tensor.data_ptr(): `tensor` of shape (3, h, w) gets R, G, B planes; with
     `chroma` of shape (ceil(h / 2), 2 * ceil(w / 2)) given, `tensor` (h, w) gets luma and `chroma` the interleaved U, V of a 4:2:0
     picture (NV12 / P010 family).  The sample type follows the dtype (float32: F32; else `sample`, native by default).  The context should
@@ -296,8 +319,16 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     DevicePicture.export_rgb, as does any RGB tensor when `chroma_pos`, `scale` or `bias` is given (see there; no grain then).  With `resize=True`
     these go through DevicePicture.export_rgb_scaled; the output size of a packed tensor is its shape[0] x shape[1] (a shape that reads both ways, (3, n, 3) or (3, n, 4), raises ValueError with these options).
     `colour` (a handle of Context.colour / Context.colour_for): float RGB tensors go through DevicePicture.export_rgb_colour; not together with
-    `grain`, `crop` or `resize`."""
+    `grain`, `crop` or `resize`.
+    `interp="bilinear"` (with `resize=True`; RGB tensors only, no `grain`, no `colour`): the output may be LARGER than the crop on either axis; the
+    call goes through DevicePicture.export_rgb_resized.  `interp=None` keeps the routes above, which refuse such a size."""
     import torch
+    if interp is not None:
+        flt = _filter_of(interp)
+        if not resize:
+            raise ValueError("interp= needs resize=True")
+        if grain is not None or colour is not None or chroma is not None:
+            raise ValueError("interp= goes through export_rgb_resized: RGB tensors only, no grain, no colour")
     if colour is not None and (grain is not None or crop is not None or resize):
         raise ValueError("colour= goes through export_rgb_colour: no grain, no crop, no resize")
     if crop is not None and not resize:
@@ -342,6 +373,9 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
     if s.dtype.itemsize != es or (not packed and [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]):
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
+    if interp is not None:
+        pic.export_rgb_resized(s, crop, chroma_pos or 0, scale, bias, row0, row1, flt)
+        return s
     if rgbx and resize:
         pic.export_rgb_scaled(s, crop, chroma_pos or 0, scale, bias, row0, row1)
         return s
@@ -358,13 +392,15 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     return s
 
 
-def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sample=None, chroma_pos=None, scale=None, bias=None):
+def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sample=None, chroma_pos=None, scale=None, bias=None, interp=None):
     """Fills one torch tensor with N pictures (or N regions: pictures may repeat) through Context.export_rgb_scaled_batch, one launch for all of them:
     `tensor` of shape (N, 3, h, w) gets R, G, B planes, (N, h, w, 3) / (N, h, w, 4) gets packed RGB / RGBA; h x w is the output size of every item and
     crops[k] = (x0, y0, w, h) (`crops` None: the whole picture) the rectangle of pics[k] that is scaled to it.  The dtype picks the sample as in
     export_to_tensor (float32: F32, float16: F16, else `sample`, native by default).  Item k is written through tensor[k]: any batch stride is fine
     (a view such as big[::2]), rows need unit stride.  ValueError for what export_to_tensor raises, for len(pics) != N, and for a shape
-    (N, 3, n, 3) or (N, 3, n, 4), which reads both ways.  Returns the surfaces."""
+    (N, 3, n, 3) or (N, 3, n, 4), which reads both ways.  `interp="bilinear"`: through Context.export_rgb_resized_batch, h x w may then be larger than
+    a crop on either axis (None: such an item makes the batch raise, as before).  Returns the surfaces."""
+    flt = None if interp is None else _filter_of(interp)
     if tensor.dim() != 4:
         raise ValueError("a batch tensor has shape (N, 3, h, w), (N, h, w, 3) or (N, h, w, 4)")
     shape = tuple(int(v) for v in tensor.shape)
@@ -396,7 +432,9 @@ def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sam
         if s.dtype.itemsize != es:
             raise ValueError("tensor dtype does not fit the surface of item %d: %s" % (k, s.dtype))
         surfaces.append(s)
-    if n:
+    if n and flt is not None:
+        pics[0].ctx.export_rgb_resized_batch(surfaces, pics, crops, chroma_pos or 0, scale, bias, flt)
+    elif n:
         pics[0].ctx.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos or 0, scale, bias)
     return surfaces
 
@@ -574,7 +612,7 @@ class Context:
     def colour_destroy(self, h):
         _chk(self.lib.dav1d_hip_colour_destroy(self.h, h), "colour_destroy")
 
-    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None):
+    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None):
         """dav1d_hip_surface_export_rgb_scaled_batch: item k gets what pics[k].export_rgb_scaled(surfaces[k], crops[k], chroma_pos, scale, bias) writes,
         all items in one launch (two when raster and twin-only pictures are mixed).  Pictures may repeat; `crops` is None (every item whole) or a
         rectangle (x0, y0, w, h) per item.  One format, one sample type and one pixel size (8 bit, or 10 / 12 bit) per batch.  Asynchronous like
@@ -587,8 +625,18 @@ class Context:
         rects = None if crops is None else (SurfaceRect * max(n, 1))(*[SurfaceRect(*[int(v) for v in r]) for r in crops])
         p = DevicePicture._rgb_params(chroma_pos, scale, bias)
         bad = C.c_int(-1)
-        rc = self.lib.dav1d_hip_surface_export_rgb_scaled_batch(self.h, n, dst, src, rects, C.byref(p), C.byref(bad))
-        _chk(rc, "surface_export_rgb_scaled_batch" + (" (item %d)" % bad.value if bad.value >= 0 else ""))
+        if _filter is None:
+            rc, what = self.lib.dav1d_hip_surface_export_rgb_scaled_batch(self.h, n, dst, src, rects, C.byref(p), C.byref(bad)), "surface_export_rgb_scaled_batch"
+        else:
+            rc = self.lib.dav1d_hip_surface_export_rgb_resized_batch(self.h, n, dst, src, rects, C.byref(p), int(_filter), C.byref(bad))
+            what = "surface_export_rgb_resized_batch"
+        _chk(rc, what + (" (item %d)" % bad.value if bad.value >= 0 else ""))
+
+    def export_rgb_resized_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_resized_batch: export_rgb_scaled_batch whose item k gets what pics[k].export_rgb_resized(surfaces[k], crops[k],
+        chroma_pos, scale, bias, filter=filter) writes — a surface may be larger than its crop on either axis, and the items of a batch may mix axes
+        that go up, down and nowhere."""
+        self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter)
 
     # ---- batched entry points (host task arrays, device arenas)
     def itx_add_batch(self, dst, tasks, coef):

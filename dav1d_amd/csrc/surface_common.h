@@ -1,5 +1,6 @@
 // What the output units share (surface.hip: the plain export; surface_grain.hip: the export with film grain fused in; surface_scale.hip: the export
-// with a crop and a scaler in front; surface_rgb.hip: tensor-ready RGB; surface_rgb_scale.hip: that behind the scaler; surface_batch.hip: many of those in one launch): the 8-sample unit and
+// with a crop and a scaler in front; surface_rgb.hip: tensor-ready RGB; surface_rgb_scale.hip: that behind the scaler; surface_batch.hip: many of those in one launch;
+// surface_resize.hip: both with axes that may go up): the 8-sample unit and
 // its loads and stores, the output sample functors, the kernel arguments and how a call is checked and turned into them.  See surface.hip for the
 // layout of a wave (8 rows x 8 units, a 64 x 8 cell of a plane).
 #pragma once
@@ -555,6 +556,7 @@ struct ScalePlane {
     int x0, y0, sw, sh;         // the window of the plane that is scaled
     int dw, dh;                 // ... to this size
     int ow, oh;                 // the cell
+    int up;                     // the resizing kernels only (surface_resize.hip): bit 0 / 1: the axis across / down goes up, through R of DESIGN.md 10.7
 };
 
 template <typename pixel> struct ScaleLds {
@@ -588,20 +590,77 @@ __device__ __forceinline__ int scale_weights(const int o, const int s, const int
     return n;
 }
 
+// A uniform value that the compiler shall not follow out of the loops around its use: what a division derives from its divisor is then made where
+// the division stands, not once per kernel and carried in vector registers through the whole cell (the resizing kernels have twice the divisions
+// of the scaling ones and would lose a wave per SIMD to that)
+__device__ __forceinline__ int used_here(int v)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(DAV1D_HIP_EMU)
+    asm volatile("" : "+s"(v));
+#endif
+    return v;
+}
+
+// taps and weights of output `o` of an axis that goes up (s source samples to d > s), the resampler R of DESIGN.md 10.7: linear interpolation with
+// half-sample centres in 12-bit weights, the two taps merged after the clamp to [0, s) — one or two taps of positive weight, 4096 in sum, on
+// consecutive indices; *first = the first of them (never decreasing in o).  With q = (o s) / d and m = 2 (o s - q d) + s - d, which lies in (-d, 2 d):
+// N = (2 o + 1) s - d = 2 d q + m, so i0 = floor(N / 2 d) is q - 1 with r = m + 2 d for a negative m, else q with r = m — one long division, as in S.
+__device__ __forceinline__ int resize_weights(const int o, const int s, const int d_, int *const first, uint16_t *const w, const int wstride)
+{
+    const int d = used_here(d_);
+    const uint64_t a = (uint64_t) o * (unsigned) s;
+    const int q = (int) (a / (unsigned) d);
+    const long long m = 2 * (long long) (a - (uint64_t) q * (unsigned) d) + s - d;
+    const int i0 = m < 0 ? q - 1 : q;                           // -1 .. s - 1
+    const uint64_t r = (uint64_t) (m < 0 ? m + 2LL * d : m);    // < 2 d
+    // w1 = (r * 4096 + d) / (2 d) = ((r * 4096) / d + 1) >> 1: a division by d, like every other one of this axis
+    const unsigned w1 = ((d < (1 << 18) ? (unsigned) r * 4096u / (unsigned) d : (unsigned) (r * 4096u / (unsigned) d)) + 1) >> 1;
+    if (i0 < 0 || i0 >= s - 1 || w1 == 0 || w1 == 4096) {
+        *first = i0 < 0 ? 0 : i0 >= s - 1 ? s - 1 : i0 + (w1 == 4096);
+        w[0] = 4096;
+        return 1;
+    }
+    *first = i0;
+    w[0] = (uint16_t) (4096 - w1); w[wstride] = (uint16_t) w1;
+    return 2;
+}
+// samples [*a0, *a1) of an axis of s samples that hold every tap of outputs [o0, o0 + n) of d, n > 0.  Through S: the hull of the taps.  `up`, through R:
+// (o s) / d - 1 <= i0(o) <= (o s) / d, so from the sample before (o0 s) / d to the one behind ((o0 + n - 1) s) / d, clamped to the axis — at most n + 2
+// samples, of which one at either end may go unused
+__device__ __forceinline__ void scale_span(const bool up, const int o0, const int n, const int s, const int d_, int *const a0, int *const a1)
+{
+    const int d = used_here(d_);
+    const uint64_t lo = (uint64_t) o0 * (unsigned) s, hi = up ? (uint64_t) (o0 + n - 1) * (unsigned) s : (uint64_t) (o0 + n) * (unsigned) s + (unsigned) d - 1;
+    const int q0 = (int) (lo / (unsigned) d), q1 = (int) (hi / (unsigned) d);
+    *a0 = up ? dv::imax(q0 - 1, 0) : q0;
+    *a1 = up ? dv::imin(q1 + 2, s) : q1;
+}
+
 // Outputs [ox0, ox0 + nox) x [j0, j1) of plane p into out[(j - oyb) * SC_OW + (o - ox0)].  Every argument is uniform in the workgroup; all of
 // its threads call.  nox <= SC_OW, oyb <= j0, j1 - oyb <= SC_OR.  HALF 0: `out` holds samples (uint16_t).  HALF 1 / 2: `out` holds pairs (uint32_t),
 // the call sets the word to the sample / adds the sample as its upper half (U, then V of the same outputs: the same thread owns the word both times).
-template <typename pixel, bool TILED, int HALF = 0, typename O = uint16_t>
+// RESIZE (surface_resize.hip): an axis whose bit of p.up is set takes its window and its weights from R instead of S; everything else is the same.
+template <typename pixel, bool TILED, int HALF = 0, typename O = uint16_t, bool RESIZE = false>
 __device__ __forceinline__ void scale_cell(ScaleLds<pixel> &L, const ScalePlane &p, const int ox0, const int nox, const int oyb, const int j0, const int j1,
                                            O *const out)
 {
     typedef Piece<8 * sizeof(pixel)> piece_t;
     if (j1 <= j0 || nox <= 0) return;
     const int tid = (int) threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int ax0 = p.x0 + (int) ((uint64_t) ox0 * (unsigned) p.sw / (unsigned) p.dw);
-    const int ax1 = p.x0 + (int) (((uint64_t) (ox0 + nox) * (unsigned) p.sw + (unsigned) p.dw - 1) / (unsigned) p.dw);
-    const int ay0 = p.y0 + (int) ((uint64_t) j0 * (unsigned) p.sh / (unsigned) p.dh);
-    const int ay1 = p.y0 + (int) (((uint64_t) j1 * (unsigned) p.sh + (unsigned) p.dh - 1) / (unsigned) p.dh);
+    int ax0, ax1, ay0, ay1;
+    const bool upx = RESIZE && (p.up & 1), upy = RESIZE && (p.up & 2);
+    if (RESIZE) {
+        scale_span(upx, ox0, nox, p.sw, p.dw, &ax0, &ax1);
+        scale_span(upy, j0, j1 - j0, p.sh, p.dh, &ay0, &ay1);
+        // (uniform, but out of the vector unit's long division: said here, the bounds and all that follows from them stay in scalar registers)
+        ax0 = __builtin_amdgcn_readfirstlane(ax0 + p.x0); ax1 = __builtin_amdgcn_readfirstlane(ax1 + p.x0);
+        ay0 = __builtin_amdgcn_readfirstlane(ay0 + p.y0); ay1 = __builtin_amdgcn_readfirstlane(ay1 + p.y0);
+    } else {
+        ax0 = p.x0 + (int) ((uint64_t) ox0 * (unsigned) p.sw / (unsigned) p.dw);
+        ax1 = p.x0 + (int) (((uint64_t) (ox0 + nox) * (unsigned) p.sw + (unsigned) p.dw - 1) / (unsigned) p.dw);
+        ay0 = p.y0 + (int) ((uint64_t) j0 * (unsigned) p.sh / (unsigned) p.dh);
+        ay1 = p.y0 + (int) (((uint64_t) j1 * (unsigned) p.sh + (unsigned) p.dh - 1) / (unsigned) p.dh);
+    }
     const int ux0 = ax0 & ~7, ry0 = ay0 & ~7;
     const int ncols = ax1 - ux0, nrows = ay1 - ry0;
     const int nU = (ncols + 7) >> 3, nUg = (nU + 7) >> 3, nRg = (nrows + 7) >> 3;
@@ -626,12 +685,12 @@ __device__ __forceinline__ void scale_cell(ScaleLds<pixel> &L, const ScalePlane 
     // ---- the weights
     if (tid < nox) {
         int i0;
-        L.nx[tid] = (uint8_t) scale_weights(ox0 + tid, p.sw, p.dw, &i0, &L.wx[0][tid], SC_OW);
+        L.nx[tid] = (uint8_t) (upx ? resize_weights(ox0 + tid, p.sw, p.dw, &i0, &L.wx[0][tid], SC_OW) : scale_weights(ox0 + tid, p.sw, p.dw, &i0, &L.wx[0][tid], SC_OW));
         L.ix[tid] = (uint16_t) (p.x0 + i0 - ux0);
     } else if (tid >= SC_OW && tid < SC_OW + (j1 - j0)) {
         const int jr = j0 - oyb + tid - SC_OW;
         int i0;
-        L.ny[jr] = (uint8_t) scale_weights(oyb + jr, p.sh, p.dh, &i0, &L.wy[0][jr], SC_OR);
+        L.ny[jr] = (uint8_t) (upy ? resize_weights(oyb + jr, p.sh, p.dh, &i0, &L.wy[0][jr], SC_OR) : scale_weights(oyb + jr, p.sh, p.dh, &i0, &L.wy[0][jr], SC_OR));
         L.iy[jr] = (uint16_t) (p.y0 + i0 - ry0);
     }
     __syncthreads();
@@ -671,7 +730,9 @@ struct ScaleGeom {
 };
 
 // the crop and the ratio: what dav1d_hip_surface_export_scaled refuses beyond what the plain export does
-inline int scale_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, ScaleGeom *const g)
+// (`up_ok`: the resizing calls of surface_resize.hip, which serve dst->w > w and dst->h > h)
+inline int scale_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, ScaleGeom *const g,
+                            const bool up_ok = false)
 {
     const int W = src->p[0].w, H = src->p[0].h;
     g->mono = src->layout == DAV1D_HIP_LAYOUT_I400;
@@ -680,7 +741,7 @@ inline int scale_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPict
     g->dw = dst->w; g->dh = dst->h;
     if (g->w <= 0 || g->h <= 0 || g->x0 < 0 || g->y0 < 0 || g->x0 > W - g->w || g->y0 > H - g->h) return -EINVAL;
     if ((g->ss_hor && (g->x0 & 1)) || (g->ss_ver && (g->y0 & 1))) return -EINVAL;
-    if (g->dw > g->w || g->dh > g->h || g->w > 8LL * g->dw || g->h > 8LL * g->dh) return -ENOTSUP;
+    if ((!up_ok && (g->dw > g->w || g->dh > g->h)) || g->w > 8LL * g->dw || g->h > 8LL * g->dh) return -ENOTSUP;
     return 0;
 }
 
@@ -697,6 +758,7 @@ ScalePlane make_scale_plane(const Dav1dHipPicture *const src, void *const *const
     p.dw = (g.dw + ssh) >> ssh; p.dh = (g.dh + ssv) >> ssv;
     p.ow = p.sw <= 2LL * p.dw ? 128 : p.sw <= 4LL * p.dw ? 64 : 32;
     p.oh = p.sh <= 4LL * p.dh ? 8 : 4;
+    p.up = (p.dw > p.sw) | (p.dh > p.sh) << 1;          // (never set where scale_geom_check ran without up_ok)
     return p;
 }
 
@@ -707,6 +769,27 @@ inline int scale_rows_needed(const ScaleGeom &g, const int src_h, const int r1)
     if (!g.mono) {
         const int sh = (g.h + g.ss_ver) >> g.ss_ver, dch = (g.dh + g.ss_ver) >> g.ss_ver, cr1 = r1 >= g.dh ? dch : r1 >> g.ss_ver;
         const long long cneed = ((long long) (g.y0 >> g.ss_ver) + ((long long) cr1 * sh + dch - 1) / dch) << g.ss_ver;
+        if (cneed > need) need = cneed;
+    }
+    return (int) (need > src_h ? src_h : need);
+}
+
+// the same for the resizing calls (dav1d_hip_surface_rgb_resized_rows_needed): on an axis that goes up, rows [0, r) of a plane read rows
+// [0, min(s, i0(r - 1) + 2)) of its window
+inline int resize_rows_of(const int r, const int s, const int d)
+{
+    if (r <= 0) return 0;
+    if (d <= s) return (int) (((long long) r * s + d - 1) / d);
+    const long long D = 2LL * d, N = (2LL * (r - 1) + 1) * s - d;
+    const long long rows = (N + D) / D + 1;          // i0 + 2
+    return (int) (rows > s ? s : rows);
+}
+inline int resize_rows_needed(const ScaleGeom &g, const int src_h, const int r1)
+{
+    long long need = g.y0 + resize_rows_of(r1, g.h, g.dh);
+    if (!g.mono) {
+        const int sh = (g.h + g.ss_ver) >> g.ss_ver, dch = (g.dh + g.ss_ver) >> g.ss_ver, cr1 = r1 >= g.dh ? dch : r1 >> g.ss_ver;
+        const long long cneed = ((long long) (g.y0 >> g.ss_ver) + resize_rows_of(cr1, sh, dch)) << g.ss_ver;
         if (cneed > need) need = cneed;
     }
     return (int) (need > src_h ? src_h : need);
@@ -752,7 +835,7 @@ __device__ __forceinline__ void rgbx_unit(const RgbArgs &a, const Out &out, cons
 // One workgroup's share of a scaled tensor-ready export: cell g (counted across, then down) of the call described by a.  Everything in a is uniform in the
 // workgroup; all of its 256 threads call.  The kernels of surface_rgb_scale.hip (a: the kernel's own argument) and surface_batch.hip (a: the item's
 // record in the batch's table) are this function behind a __shared__ ScaleLds.
-template <typename pixel, bool TILED, typename Out>
+template <typename pixel, bool TILED, typename Out, bool RESIZE = false>
 __device__ __forceinline__ void scale_rgbx_cell(ScaleLds<pixel> &L, const ScaleRgbxArgs &a, const int g, const Out &out)
 {
     typedef typename Out::T T;
@@ -765,8 +848,8 @@ __device__ __forceinline__ void scale_rgbx_cell(ScaleLds<pixel> &L, const ScaleR
     const int hj0 = dv::imax(cj0 - a.hyu, 0), hj1 = dv::imin(cj1 + a.hyd, pc.dh);
     uint32_t *const pairs = L.pair.uv;
     if (!a.c.mono) {
-        scale_cell<pixel, TILED, 1, uint32_t>(L, a.pl[1], hx0, hx1 - hx0, hj0, hj0, hj1, pairs);
-        scale_cell<pixel, TILED, 2, uint32_t>(L, a.pl[2], hx0, hx1 - hx0, hj0, hj0, hj1, pairs);
+        scale_cell<pixel, TILED, 1, uint32_t, RESIZE>(L, a.pl[1], hx0, hx1 - hx0, hj0, hj0, hj1, pairs);
+        scale_cell<pixel, TILED, 2, uint32_t, RESIZE>(L, a.pl[2], hx0, hx1 - hx0, hj0, hj0, hj1, pairs);
     }
     const bool hf = a.hx != 0, vf = a.hyd != 0;
     const uint32_t grey = (uint32_t) a.c.mid * 0x10001u;
@@ -778,7 +861,7 @@ __device__ __forceinline__ void scale_rgbx_cell(ScaleLds<pixel> &L, const ScaleR
         if (j1 <= j0) continue;
         for (int lx = lx0; lx < lx1; lx += py.ow) {
             const int nox = dv::imin(py.ow, lx1 - lx);
-            scale_cell<pixel, TILED>(L, py, lx, nox, lyb, j0, j1, L.pair.y);
+            scale_cell<pixel, TILED, 0, uint16_t, RESIZE>(L, py, lx, nox, lyb, j0, j1, L.pair.y);
             const int nun = (nox + 7) >> 3;
             for (int it = (int) threadIdx.x; it < (j1 - j0) * nun; it += 256) {
                 const int j = it / nun, u = it - j * nun, y = j0 + j, x = lx + u * 8, n = nox - u * 8;
@@ -829,11 +912,12 @@ __device__ __forceinline__ void scale_rgbx_cell(ScaleLds<pixel> &L, const ScaleR
 
 // the union of what dav1d_hip_surface_export_rgb and dav1d_hip_surface_export_scaled refuse
 inline int rgbx_scaled_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop,
-                                  const Dav1dHipRgbParams &p, const int row0, const int row1, SurfaceCall *const call, ScaleGeom *const g)
+                                  const Dav1dHipRgbParams &p, const int row0, const int row1, SurfaceCall *const call, ScaleGeom *const g,
+                                  const bool up_ok = false)
 {
     if (const int rc = surface_args_check(dst, src, row0, row1, call, true, true)) return rc;
     if (const int rc = rgb_params_check(dst, p)) return rc;
-    return scale_geom_check(dst, src, crop, g);
+    return scale_geom_check(dst, src, crop, g, up_ok);
 }
 
 // the kernel's arguments for destination luma rows [row0, row1) of a checked call; *n_groups = its workgroups (a cell of Q's chroma planes each)

@@ -369,6 +369,50 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_scaled_batch(Dav1dHipContext *c, 
                                                             const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
                                                             const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */,
                                                             int *bad_item /* may be NULL */);
+/* The same exports at ANY size (dav1d_amd/csrc/surface_resize.hip): dst->w > w and dst->h > h are served.  The calls above keep
+ * refusing them; these are entry points of their own.
+ * The resampler R works per plane and per axis, independently, the vertical pass first, on the windows of dav1d_hip_surface_export_scaled: for plane pl
+ * with (ssh, ssv) the window at (x0 >> ssh, y0 >> ssv) of size ((w + ssh) >> ssh, (h + ssv) >> ssv) goes to ((dst->w + ssh) >> ssh, (dst->h + ssv) >>
+ * ssv).  An axis has source length s and destination length d.
+ *   d <= s: S's area rule above, unchanged (s <= 8 d).
+ *   d > s:  linear interpolation with half-sample centres.  For output o: N = (2 o + 1) s - d (may be negative), D = 2 d, i0 = floor(N / D) (at least
+ *           -1), r = N - i0 D in [0, D), w1 = (r * 4096 + d) / D (an integer division), w0 = 4096 - w1.  The taps are (cl(i0, s), w0) and
+ *           (cl(i0 + 1, s), w1), cl(i, n) = min(max(i, 0), n - 1); taps that land on one index after the clamp add up, a tap of weight 0 is not read.
+ *           The weights are never negative and sum to 4096; after merging there are one or two taps, on consecutive indices inside [0, s): nothing
+ *           outside the crop window of the plane is ever read.
+ * The arithmetic after the weights is S's: t = (sum wy P + 8) >> 4, out = (sum wx t + (1 << 19)) >> 20; no clip is needed.  A constant plane stays
+ * constant; s == 1 gives that sample everywhere; an exact 2:1 upscale has the interior weights 1024 / 3072 (output 2k takes samples k - 1 and k at
+ * 1 : 3, output 2k + 1 samples k and k + 1 at 3 : 1) and its first and last outputs are the edge samples.  A plane can go up on one axis and down (or
+ * nowhere) on the other, and luma and chroma can fall on different sides: h = 3, dst->h = 4 at 4:2:0 is luma 3 -> 4 and chroma 2 -> 2.
+ * The limitation of dav1d_hip_surface_export_rgb_scaled holds here as well: every plane is resampled on its own grid, so Q's chroma lies up to half a
+ * SOURCE luma sample away from the site chroma_pos names; a phase-corrected chroma scaler is not built.  No film grain.
+ * dav1d_hip_surface_export_rgb_resized writes byte for byte what dav1d_hip_surface_export_rgb(c, dst, Q, params, drow0, drow1) would write, Q's planes
+ * being R of the crop windows; Q never reaches memory.  Everything else is dav1d_hip_surface_export_rgb_scaled's: the formats, the samples,
+ * chroma_pos 0 / 1 / 2 with cl() against Q's chroma size, normalisation, alpha, the matrix and range rules, even band rows, one launch on the
+ * context's stream, dav1d_hip_last_kernel_ms, a const `src` (a DAV1D_HIP_TWIN_ONLY picture stays one), no allocation, no host wait, no table made on
+ * the host, nothing written outside the visible destination samples of the rows asked for.  Where every plane has d <= s on both axes the bytes are
+ * those of dav1d_hip_surface_export_rgb_scaled.  `filter` is DAV1D_HIP_RESIZE_BILINEAR.
+ * Errors, before anything is enqueued: those of dav1d_hip_surface_export_rgb_scaled, in its order and with its codes, except that dst->w > w and
+ * dst->h > h are served (w > 8 dst->w and h > 8 dst->h are still -ENOTSUP, whatever the other axis does); then -ENOTSUP for an unknown filter;
+ * then -EXDEV for a picture of another device.
+ * dav1d_hip_surface_rgb_resized_rows_needed is host arithmetic like dav1d_hip_surface_rgb_scaled_rows_needed, for destination rows [0, r) with the
+ * same r: on an axis that goes up rows [0, r) of a plane need rows [0, min(s, i0(r - 1) + 2)) of its window, else S's ceil(r s / d); luma and chroma
+ * are combined as there.
+ * dav1d_hip_surface_export_rgb_resized_batch is dav1d_hip_surface_export_rgb_scaled_batch with this contract per item — the same uniformity rules,
+ * DAV1D_HIP_SURFACE_BATCH_MAX, staging ring, two launches when raster and twin-only sources mix, and *bad_item; the items of one batch may mix axes
+ * that go up, down and nowhere freely.  An unknown filter is a fault of the call as a whole (-ENOTSUP, *bad_item = -1), found after c and n are
+ * checked and before any item is looked at. */
+enum Dav1dHipResizeFilter { DAV1D_HIP_RESIZE_BILINEAR = 0 };   /* anything else: -ENOTSUP */
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_resized(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                       const Dav1dHipSurfaceRect *crop /* NULL = everything */,
+                                                       const Dav1dHipRgbParams *params /* NULL = all zero */, int filter, int drow0, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_rgb_resized_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
+                                                            const Dav1dHipRgbParams *params, int filter, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_resized_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst /* [n] */,
+                                                             const Dav1dHipPicture *const *src /* [n] */,
+                                                             const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
+                                                             const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */, int filter,
+                                                             int *bad_item /* may be NULL */);
 /* Colour-managed RGB (dav1d_amd/csrc/surface_colour.hip): dav1d_hip_surface_export_rgb followed, in the same pass, by the stage
  * every colour pipeline has — a 1-D table, a 3x3 matrix, a 1-D table ("degamma, CSC, regamma") — with tables of the caller.
  * Definition.  Let (R, G, B) be the integers in [0, max] that dav1d_hip_surface_export_rgb computes for a pixel (the same matrix, range, sited chroma,
