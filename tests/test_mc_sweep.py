@@ -334,11 +334,12 @@ def test_extremal_reference_content(ctx, bpc):
 REGION = 64
 
 
-def enumerated_frame(bpc, regions_per_size, cols, seed):
+def enumerated_frame(bpc, regions_per_size, cols, seed, compound=None):
     """An inter frame in the layout of synth_frames.make_frame (64x64 regions of one luma block size each, 4:2:0, one transform per
     block), with ENUMERATED filters and phases: the single-reference blocks of every (plane class, block size) step through a
     permutation of all (filter_2d, mx, my); every fourth block of luma 8x8 and up is an avg compound whose two references step through
-    the phases independently.  regions_per_size: {luma block size: number of regions}."""
+    the phases independently.  regions_per_size: {luma block size: number of regions}.  compound: None (every compound is an avg), or
+    a function (serial number of the compound in the frame, its filter_2d) -> (COMP_TASK kind, arg) that decides each one."""
     rng = np.random.default_rng(seed)
     sizes = [s for s, n in regions_per_size.items() for _ in range(n)]
     rng.shuffle(sizes)
@@ -393,6 +394,8 @@ def enumerated_frame(bpc, regions_per_size, cols, seed):
                     e["kind"], e["dst_off"] = 1, prep_off
                     if r == 0:
                         ct[nc]["dst_off"], ct[nc]["tmp1_off"], ct[nc]["w"], ct[nc]["h"], ct[nc]["plane"] = dst_off, prep_off, pw, pw, pl
+                        if compound is not None:
+                            ct[nc]["kind"], ct[nc]["arg"] = compound(sum(len(c) for c in comp) + nc, f)
                         first = (f, mx, my)
                     else:
                         ct[nc]["tmp2_off"] = prep_off

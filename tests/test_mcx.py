@@ -15,6 +15,49 @@ def _need_ref():
     return util.default_oracle()
 
 
+def _oracle_warp(oracle, bpc, refplane, vis_w, vis_h, task, dst_block=None, tmp=None):
+    """One 8x8 block of the reference driver's warp_affine() on a host plane (2-D array, padded; vis_w x vis_h visible): emu_edge of
+    the 15x15 window when it leaves the plane (src/recon_tmpl.c:1146-1163), then warp8x8 into dst_block or warp8x8t into tmp (int16,
+    row stride task["tmp_stride"])."""
+    pd = refplane.dtype
+    bps = pd.itemsize
+    dx, dy, mx, my = (int(task[k]) for k in ("src_x", "src_y", "mx", "my"))
+    abcd = np.ascontiguousarray(task["abcd"], dtype=np.int16)
+    if dx < 3 or dx + 8 + 4 > vis_w or dy < 3 or dy + 8 + 4 > vis_h:
+        emu = np.zeros((16, 32), pd)
+        oracle.call(bpc, "emu_edge", 0, 0, 15, 15, vis_w, vis_h, dx - 3, dy - 3, emu.ctypes.data, 32 * bps,
+                    refplane.ctypes.data, refplane.strides[0])
+        src_ptr, src_stride = emu.ctypes.data + (32 * 3 + 3) * bps, 32 * bps
+    else:
+        src_ptr, src_stride = refplane.ctypes.data + dy * refplane.strides[0] + dx * bps, refplane.strides[0]
+    if dst_block is not None:
+        oracle.call(bpc, "warp8x8", 0, 0, dst_block.ctypes.data, dst_block.strides[0], src_ptr, src_stride, abcd, mx, my)
+    else:
+        oracle.call(bpc, "warp8x8t", 0, 0, tmp.ctypes.data, int(task["tmp_stride"]), src_ptr, src_stride, abcd, mx, my)
+
+
+def _oracle_mc_scaled(oracle, bpc, refplane, vis_w, vis_h, task, dst_block=None, tmp=None):
+    """The scaled branch of the reference driver's mc() on a host plane (src/recon_tmpl.c:990-1047): emu_edge of the source window when
+    it leaves the plane, then mc_scaled into dst_block (pixels, any row stride) or mct_scaled into tmp (int16, row stride w)."""
+    pd = refplane.dtype
+    bps = pd.itemsize
+    w, h, mx, my, step_x, step_y, f = (int(task[k]) for k in ("w", "h", "mx", "my", "dx", "dy", "filter_2d"))
+    left, top = int(task["src_x"]), int(task["src_y"])
+    right = left + ((mx + (w - 1) * step_x) >> 10) + 1
+    bottom = top + ((my + (h - 1) * step_y) >> 10) + 1
+    if left < 3 or top < 3 or right + 4 > vis_w or bottom + 4 > vis_h:
+        emu = np.zeros((bottom - top + 8, 320), pd)
+        oracle.call(bpc, "emu_edge", 0, 0, right - left + 7, bottom - top + 7, vis_w, vis_h, left - 3, top - 3,
+                    emu.ctypes.data, 320 * bps, refplane.ctypes.data, refplane.strides[0])
+        src_ptr, src_stride = emu.ctypes.data + (320 * 3 + 3) * bps, 320 * bps
+    else:
+        src_ptr, src_stride = refplane.ctypes.data + top * refplane.strides[0] + left * bps, refplane.strides[0]
+    if dst_block is not None:
+        oracle.call(bpc, "mc_scaled", f, 0, dst_block.ctypes.data, dst_block.strides[0], src_ptr, src_stride, w, h, mx, my, step_x, step_y)
+    else:
+        oracle.call(bpc, "mct_scaled", f, 0, tmp.ctypes.data, src_ptr, src_stride, w, h, mx, my, step_x, step_y)
+
+
 @pytest.mark.parametrize("bpc", [8, 10, 12])
 def test_blend_matches_reference(ctx, bpc):
     """OBMC / inter-intra flow: mc PUT_TMP into the scratch arena, then blend / blend_h / blend_v onto dst."""
@@ -121,7 +164,6 @@ def test_warp_matches_reference(ctx, bpc):
     oracle = _need_ref()
     rng = np.random.default_rng(40 + bpc)
     pd = util.pix_dtype(bpc)
-    bps = pd().itemsize
     vis_w, vis_h = 120, 90
     ref = ctx.picture(vis_w, vis_h, api.LAYOUT_I400, bpc)
     refplane = rng.integers(0, 1 << bpc, size=ref.padded_shape(0)).astype(pd)
@@ -141,22 +183,14 @@ def test_warp_matches_reference(ctx, bpc):
         dy = int(rng.choice([-7, 0, 2, int(rng.integers(3, vis_h - 12)), vis_h - 10, vis_h + 3]))
         mx, my = (int(rng.integers(0, 0x2000)) - 0xa00 for _ in range(2))
         abcd = (rng.integers(0, 0x2000, size=4) - 0xa00).astype(np.int16)
-        # the driver's fetch (src/recon_tmpl.c:1146-1163)
-        if dx < 3 or dx + 8 + 4 > vis_w or dy < 3 or dy + 8 + 4 > vis_h:
-            emu = np.zeros((16, 32), pd)
-            oracle.call(bpc, "emu_edge", 0, 0, 15, 15, vis_w, vis_h, dx - 3, dy - 3, emu.ctypes.data, 32 * bps,
-                        refplane.ctypes.data, refplane.strides[0])
-            src_ptr, src_stride = emu.ctypes.data + (32 * 3 + 3) * bps, 32 * bps
-        else:
-            src_ptr, src_stride = refplane.ctypes.data + dy * refplane.strides[0] + dx * bps, refplane.strides[0]
+        tasks[i] = (0, dx, dy, mx, my, abcd, 64, kind, 0, 0, (0, 0, 0))
         if kind == 0:
             off = by * 8 * sp + bx * 8
-            blk = want[by * 8:, bx * 8:]
-            oracle.call(bpc, "warp8x8", 0, 0, blk.ctypes.data, want.strides[0], src_ptr, src_stride, abcd, mx, my)
+            _oracle_warp(oracle, bpc, refplane, vis_w, vis_h, tasks[i], dst_block=want[by * 8:, bx * 8:])
         else:
             off = by * 8 * 64 + bx * 8
-            oracle.call(bpc, "warp8x8t", 0, 0, want_prep[off:].ctypes.data, 64, src_ptr, src_stride, abcd, mx, my)
-        tasks[i] = (off, dx, dy, mx, my, abcd, 64, kind, 0, 0, (0, 0, 0))
+            _oracle_warp(oracle, bpc, refplane, vis_w, vis_h, tasks[i], tmp=want_prep[off:])
+        tasks[i]["dst_off"] = off
     prep = ctx.buffer(64 * 64 * 2)
     prep.zero()
     ctx.warp_batch(dst, [ref], tasks, prep)
@@ -172,7 +206,6 @@ def test_mc_scaled_matches_reference(ctx, bpc, kind):
     oracle = _need_ref()
     rng = np.random.default_rng(60 + bpc * 2 + kind)
     pd = util.pix_dtype(bpc)
-    bps = pd().itemsize
     vis_w, vis_h = 300, 280
     ref = ctx.picture(vis_w, vis_h, api.LAYOUT_I400, bpc)
     refplane = rng.integers(0, 1 << bpc, size=ref.padded_shape(0)).astype(pd)
@@ -203,27 +236,18 @@ def test_mc_scaled_matches_reference(ctx, bpc, kind):
         step_y = int(rng.choice([512, 1024, 2048, int(rng.integers(1, 2049))]))
         left = int(rng.choice([-20, -2, 1, int(rng.integers(3, vis_w)), vis_w - 5, vis_w + 3]))
         top = int(rng.choice([-11, 0, 2, int(rng.integers(3, vis_h)), vis_h - 3, vis_h + 8]))
-        right = left + ((mx + (w - 1) * step_x) >> 10) + 1
-        bottom = top + ((my + (h - 1) * step_y) >> 10) + 1
-        if left < 3 or top < 3 or right + 4 > vis_w or bottom + 4 > vis_h:
-            emu = np.zeros((bottom - top + 8, 320), pd)
-            oracle.call(bpc, "emu_edge", 0, 0, right - left + 7, bottom - top + 7, vis_w, vis_h, left - 3, top - 3,
-                        emu.ctypes.data, 320 * bps, refplane.ctypes.data, refplane.strides[0])
-            src_ptr, src_stride = emu.ctypes.data + (320 * 3 + 3) * bps, 320 * bps
-        else:
-            src_ptr, src_stride = refplane.ctypes.data + top * refplane.strides[0] + left * bps, refplane.strides[0]
         f = int(rng.integers(0, 10))
+        tasks[k] = (0, left, top, mx, my, step_x, step_y, w, h, f, kind, 0, 0, (0, 0))
         if kind == 0:
             off = y * sp + x
-            blk = want[y:, x:]
-            oracle.call(bpc, "mc_scaled", f, 0, blk.ctypes.data, want.strides[0], src_ptr, src_stride, w, h, mx, my, step_x, step_y)
+            _oracle_mc_scaled(oracle, bpc, refplane, vis_w, vis_h, tasks[k], dst_block=want[y:, x:])
         else:
             off = prep_off
             tmp = np.zeros(w * h, np.int16)
-            oracle.call(bpc, "mct_scaled", f, 0, tmp.ctypes.data, src_ptr, src_stride, w, h, mx, my, step_x, step_y)
+            _oracle_mc_scaled(oracle, bpc, refplane, vis_w, vis_h, tasks[k], tmp=tmp)
             want_prep.append(tmp)
             prep_off += w * h
-        tasks[k] = (off, left, top, mx, my, step_x, step_y, w, h, f, kind, 0, 0, (0, 0))
+        tasks[k]["dst_off"] = off
         x += w
         row_h = max(row_h, h)
         k += 1
