@@ -334,12 +334,14 @@ def test_extremal_reference_content(ctx, bpc):
 REGION = 64
 
 
-def enumerated_frame(bpc, regions_per_size, cols, seed, compound=None):
+def enumerated_frame(bpc, regions_per_size, cols, seed, compound=None, transforms=None):
     """An inter frame in the layout of synth_frames.make_frame (64x64 regions of one luma block size each, 4:2:0, one transform per
     block), with ENUMERATED filters and phases: the single-reference blocks of every (plane class, block size) step through a
     permutation of all (filter_2d, mx, my); every fourth block of luma 8x8 and up is an avg compound whose two references step through
     the phases independently.  regions_per_size: {luma block size: number of regions}.  compound: None (every compound is an avg), or
-    a function (serial number of the compound in the frame, its filter_2d) -> (COMP_TASK kind, arg) that decides each one."""
+    a function (serial number of the compound in the frame, its filter_2d) -> (COMP_TASK kind, arg) that decides each one.
+    transforms: None (DCT_DCT, coefficients and eob of synth_frames.gen_coefs), or a function (plane class, tx, number of blocks) ->
+    (coefficient slabs [n, coefficients], eob [n], txtp [n]) that decides the residual of every block of a (plane class, size)."""
     rng = np.random.default_rng(seed)
     sizes = [s for s, n in regions_per_size.items() for _ in range(n)]
     rng.shuffle(sizes)
@@ -411,11 +413,11 @@ def enumerated_frame(bpc, regions_per_size, cols, seed, compound=None):
         mc.append(t[:nt])
         comp.append(ct[:nc])
         tx = synth.SQ_TX[pw]
-        cf, eob = synth.gen_coefs(rng, tx, n, bpc)
+        cf, eob, txtp = synth.gen_coefs(rng, tx, n, bpc) + (0,) if transforms is None else transforms(cls, tx, n)
         it = np.zeros(n, api.ITX_TASK)
         it["dst_off"] = [b[2] * geo[b[0]][0] + b[1] for b in lst]
         it["cf_off"] = cf_off + np.arange(n, dtype=np.int64) * cf.shape[1]
-        it["eob"], it["tx"] = eob, tx
+        it["eob"], it["tx"], it["txtp"] = eob, tx, txtp
         it["plane"] = [b[0] for b in lst]
         itx.append(it)
         coefs.append(cf.reshape(-1))

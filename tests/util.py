@@ -260,12 +260,12 @@ def tx_class(txtp):
     return 0
 
 
-def gen_itx_coefs(rng, tx, txtp, bpc, subsh):
-    """Coefficients in the valid dynamic range + a consistent eob, in the reference slab
-    layout (column-major, min(w,32) x min(h,32)).  Mirrors ftx()/copy_subcoefs()."""
+def fwd_itx_coefs(rng, tx, txtp, bpc, amp=None):
+    """The forward transform of a random residual within +-amp (bitdepth_max when None) as an int64 slab in the reference layout
+    (column-major, min(w,32) x min(h,32)): every coefficient present, in the valid dynamic range.  Mirrors ftx()."""
     w, h = TX_W[tx], TX_H[tx]
     sw, sh = min(w, 32), min(h, 32)
-    bdmax = (1 << bpc) - 1
+    bdmax = (1 << bpc) - 1 if amp is None else amp
     res = rng.integers(-bdmax, bdmax + 1, size=(h, w)).astype(np.float64)
     k1, k2 = _FWD[txtp]
     scale = _SCALE[int(np.log2(w * h)) - 4]
@@ -275,6 +275,28 @@ def gen_itx_coefs(rng, tx, txtp, bpc, subsh):
     buf = np.zeros(sw * sh, np.int64)
     for x in range(sw):
         buf[x * sh:(x + 1) * sh] = np.floor(out[:sh, x] + 0.5)
+    return buf
+
+
+def scan_order(tx, txtp):
+    """slab index of scan position i = 0 .. min(w,32) * min(h,32) - 1 for the type's class: dav1d_scans for the 2-D classes, i for
+    the H classes, (i & (sw-1)) * sh + (i >> log2(sw)) for the V classes (reference src/recon_tmpl.c:458-496, 548-575)."""
+    sw, sh = min(TX_W[tx], 32), min(TX_H[tx], 32)
+    i = np.arange(sw * sh, dtype=np.int64)
+    cls = tx_class(txtp)
+    if cls == 0:
+        return scans()[tx].astype(np.int64)
+    if cls == 1:
+        return i
+    return (i & (sw - 1)) * sh + (i >> int(np.log2(sw)))
+
+
+def gen_itx_coefs(rng, tx, txtp, bpc, subsh):
+    """Coefficients in the valid dynamic range + a consistent eob, in the reference slab
+    layout (column-major, min(w,32) x min(h,32)).  Mirrors ftx()/copy_subcoefs()."""
+    w, h = TX_W[tx], TX_H[tx]
+    sw, sh = min(w, 32), min(h, 32)
+    buf = fwd_itx_coefs(rng, tx, txtp, bpc)
     # ---- copy_subcoefs
     scan = scans()[tx]
     cls = tx_class(txtp)
