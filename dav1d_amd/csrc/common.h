@@ -337,6 +337,53 @@ struct PxRead {
     __device__ __forceinline__ PxRead operator-(const int k) const { return PxRead{ p - k }; }
 };
 
+// ---- accesses the compiler is TOLD go to global memory.  A pointer it cannot trace back to one kernel argument — a per-lane select between
+// plane pointers, an address put together from two LDS dwords — is a generic one to it: flat_load / flat_store, which are issued to the LDS
+// path as well and count in lgkmcnt next to vmcnt.  Picture planes, the prep arena and the lists never live anywhere but in global memory
+// (the one exception, intra_sb.hip's image in LDS, goes through PxRead above).  T: any trivially copyable type of 1, 2, 4, 8 or 16 bytes;
+// the access keeps T's own alignment (the packed window loads of mc_body.h are 1- or 2-byte aligned).
+#ifndef DAV1D_HIP_EMU
+template <int BYTES> struct GlobalWord;
+template <> struct GlobalWord<1> { typedef uint8_t type; };
+template <> struct GlobalWord<2> { typedef uint16_t type; };
+template <> struct GlobalWord<4> { typedef uint32_t type; };
+template <> struct GlobalWord<8> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
+template <> struct GlobalWord<16> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
+#endif
+template <typename T>
+__device__ __forceinline__ T ld_global(const T *p) {
+#ifdef DAV1D_HIP_EMU
+    return *p;
+#else
+    typedef typename GlobalWord<sizeof(T)>::type word_t __attribute__((aligned(alignof(T))));
+    return __builtin_bit_cast(T, *(__attribute__((address_space(1))) const word_t *) p);
+#endif
+}
+template <typename T>
+__device__ __forceinline__ void st_global(T *p, const T v) {
+#ifdef DAV1D_HIP_EMU
+    *p = v;
+#else
+    typedef typename GlobalWord<sizeof(T)>::type word_t __attribute__((aligned(alignof(T))));
+    *(__attribute__((address_space(1))) word_t *) p = __builtin_bit_cast(typename GlobalWord<sizeof(T)>::type, v);
+#endif
+}
+
+// A member of a picture's per-plane arrays for a plane only known at run time.  The three members are read FIRST, each by its constant index,
+// and the VALUE is picked.  Spelled as a chain of conditional operators over the members themselves (pl == 0 ? p.stride[0] : ...) the loads
+// sit in the arms of the chain, the compiler merges them into one load through a selected address — a run-time index again — and the whole
+// kernel argument gets a copy in scratch memory to be indexed (64 bytes per lane, written by every wave before it does anything else:
+// DESIGN 9).  With a wave-uniform plane (a readlane, a one-block wave's record) the pick is a scalar select.
+__device__ __forceinline__ int plane_stride(const DevPlanes &p, const int pl) {
+    const int s0 = p.stride[0], s1 = p.stride[1], s2 = p.stride[2];
+    return pl == 0 ? s0 : pl == 1 ? s1 : s2;
+}
+template <typename pixel>
+__device__ __forceinline__ pixel *plane_data(const DevPlanes &p, const int pl) {
+    void *const d0 = p.data[0], *const d1 = p.data[1], *const d2 = p.data[2];
+    return reinterpret_cast<pixel *>(pl == 0 ? d0 : pl == 1 ? d1 : d2);
+}
+
 // x, y of a pixel offset in a plane (off < 2^28, stride < 2^15) without the integer divider: one float quotient, corrected
 __device__ __forceinline__ void off_to_xy(const uint32_t off, const int stride, int &x, int &y) {
     int q = (int) ((float) off / (float) stride);
@@ -350,6 +397,15 @@ __device__ __forceinline__ void off_to_xy(const uint32_t off, const int stride, 
 
 // This lane's index in its wave
 __device__ __forceinline__ int lane_id() { return (int) (threadIdx.x & 63); }
+
+// v, as a value the compiler knows nothing about: what is computed from it is computed HERE, not hoisted out of an enclosing loop to
+// occupy registers through all of it
+__device__ __forceinline__ int fresh(int v) {
+#ifndef DAV1D_HIP_EMU
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
 
 // the value lane `lane` (the same for every lane that asks: a loop counter of an unrolled loop, a scalar) holds, as a scalar
 __device__ __forceinline__ int readlane(const int v, const int lane) {

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(64) void itx_add_kernel(const DevPlanes dst, const 
                                                      const int n, coef *__restrict__ cf, const int bitdepth_max)
 {
     __shared__ __attribute__((aligned(16))) int tmp_s[itx_lds_ints<TX>()];
-    itx_body<TX, pixel, coef>(dst, tasks, n, cf, bitdepth_max, (int) dv::xcd_chunk_id(blockIdx.x, gridDim.x), tmp_s);
+    itx_body<TX, pixel, coef, false, false, false, true>(dst, tasks, n, cf, bitdepth_max, (int) dv::xcd_chunk_id(blockIdx.x, gridDim.x), tmp_s);
 }
 
 // The same with the sums leaving through an LDS tile in row pieces (tile_write_out, itx_body.h) — to the raster planes and, when
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(64) void itx_add_wide_kernel(const DevPlanes dst, c
     const bool twin_only = twin.tiled == 2;
     uint32_t toff = 0;
     int tpl = 0;
-    if (twin_only) itx_body<TX, pixel, coef, false, true>(twin, tasks, n, cf, bitdepth_max, group, tmp_s, tile, true, &toff, &tpl);
-    else itx_body<TX, pixel, coef, false, true>(dst, tasks, n, cf, bitdepth_max, group, tmp_s, tile, false, &toff, &tpl);
+    if (twin_only) itx_body<TX, pixel, coef, false, true, false, true>(twin, tasks, n, cf, bitdepth_max, group, tmp_s, tile, true, &toff, &tpl);
+    else itx_body<TX, pixel, coef, false, true, false, true>(dst, tasks, n, cf, bitdepth_max, group, tmp_s, tile, false, &toff, &tpl);
     dv::wave_sync();
     DV_PHASE(512 + TX * 16 + 6);        // (the body's own marks, then the wait for the sums in the tile)
     tile_write_out<W, H, BPW, pixel>(tile, tasks + block0, dv::imin(BPW, n - block0), dst, twin, twin.data[0] != nullptr, !twin_only, toff, tpl);
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64) void itx_multi_kernel(const DevPlanes dst, cons
 #pragma unroll
     for (int k = 1; k < 19; k++) b = g >= seg.grp[k] ? k : b;
     const int first = seg.off[b], cnt = seg.off[b + 1] - first, group = g - seg.grp[b];
-#define CASE(T) case T: itx_body<T, pixel, coef>(dst, tasks + first, cnt, cf, bitdepth_max, group, tmp_s); break;
+#define CASE(T) case T: itx_body<T, pixel, coef, false, false, false, true>(dst, tasks + first, cnt, cf, bitdepth_max, group, tmp_s); break;
     switch (b) {
         CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9)
         CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18)

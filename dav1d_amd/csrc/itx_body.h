@@ -133,6 +133,16 @@ __device__ __forceinline__ void itx_prefetch_coefs(ItxPre<TX, coef> &pre, const 
     if (dconly && l == 0) pre.dc = gcf[0];
 }
 
+// A block's record with ONE 16-byte load.  The structure's own alignment is 4 (its widest member), and read member by member a record
+// arrives as five narrow loads (8 + 2 + 2 + 2 + 1 bytes) in the waves where every lane fetches its own block's; p must be 16-byte aligned.
+static_assert(sizeof(Dav1dHipItxTask) == 16, "a record is one 16-byte load");
+__device__ __forceinline__ Dav1dHipItxTask itx_task_load16(const Dav1dHipItxTask *p) {
+    const uint4 raw = dv::ld_global(reinterpret_cast<const uint4 *>(p));
+    Dav1dHipItxTask t;
+    __builtin_memcpy(&t, &raw, sizeof(t));
+    return t;
+}
+
 // The wave `group` of the blocks of ONE transform size: blocks [group * BPW, group * BPW + BPW) of tasks[0 .. n).
 // PRED_LDS (fused prediction + residual kernels): the pixels the residual is added to come from pred_s (block `sub` of the
 // wave, W x H, row stride W) instead of the picture; the sum still goes to the picture.
@@ -141,7 +151,9 @@ __device__ __forceinline__ void itx_prefetch_coefs(ItxPre<TX, coef> &pre, const 
 // tsrc (with COH, without PRED_LDS): `dst` holds the planes of the picture's tiled twin (8x8 tiles of 64 consecutive pixels, mc_body.h)
 // and the pixels the residual is added to are read from there — a frame whose pictures live in the twin only (DAV1D_HIP_TWIN_ONLY).
 // PRE: the record and the coefficients were fetched ahead of time (`pre`, ItxPre above).
-template <int TX, typename pixel, typename coef, bool PRED_LDS = false, bool COH = false, bool PRE = false>
+// REC16: tasks[] is a list in device memory whose records are 16-byte aligned (the lists of lists.h: hipMalloc'ed arrays of 16-byte records) —
+// a lane fetches its block's record with one 16-byte load; false for a record that sits inside another structure (intra_flow.hip, intra_sb.hip).
+template <int TX, typename pixel, typename coef, bool PRED_LDS = false, bool COH = false, bool PRE = false, bool REC16 = false>
 __device__ __forceinline__ void itx_body(const DevPlanes &dst, const Dav1dHipItxTask *__restrict__ tasks,
                                          const int n, coef *__restrict__ cf, const int bitdepth_max, const int group, int *tmp_s,
                                          const pixel *pred_s = nullptr, const bool tsrc = false, uint32_t *task_off = nullptr, int *task_plane = nullptr,
@@ -173,6 +185,7 @@ __device__ __forceinline__ void itx_body(const DevPlanes &dst, const Dav1dHipItx
     Dav1dHipItxTask t;
     if (PRE) t = pre->t;
     else if (BPW == 1) t = tasks[__builtin_amdgcn_readfirstlane(live ? ti : 0)];   // one block per wave: record in SGPRs
+    else if (REC16) t = itx_task_load16(tasks + (live ? ti : 0));
     else t = tasks[live ? ti : 0];
 
     // (tile_write_out wants the blocks' positions: the lanes that hold a block's record hand them over, no second trip to memory)
@@ -186,19 +199,21 @@ __device__ __forceinline__ void itx_body(const DevPlanes &dst, const Dav1dHipItx
 
     coef *const gcf = cf + t.cf_off;
     int *const tmp = tmp_s + sub * SH * TS;
-    pixel *const d = reinterpret_cast<pixel *>(dst.data[t.plane]) + t.dst_off + l;
-    const int stride = dst.stride[t.plane];
+    // (the block's plane: picked among the members' values, dv::plane_stride — never an index into the kernel argument)
+    pixel *const dplane = dv::plane_data<pixel>(dst, t.plane);
+    pixel *const d = dplane + t.dst_off + l;
+    const int stride = dv::plane_stride(dst, t.plane);
     // tsrc: this lane's column of the block in the tiled plane — pixel (X, Y) lives at (Y & ~7) * stride + (X >> 3) * 64 + (Y & 7) * 8 + (X & 7)
     int tbx = 0, tby = 0;
     if (!PRED_LDS && COH && tsrc && live) dv::off_to_xy(t.dst_off, stride, tbx, tby);
-    const pixel *const tcol = reinterpret_cast<const pixel *>(dst.data[t.plane]) + ((((tbx + l) >> 3) << 6) + ((tbx + l) & 7));
+    const pixel *const tcol = dplane + ((((tbx + l) >> 3) << 6) + ((tbx + l) & 7));
     auto load_dst = [&](pixel (&px)[H]) {
         if (!PRED_LDS && COH && tsrc) {
 #pragma unroll
-            for (int y = 0; y < H; y++) px[y] = tcol[dv::mul_i24((tby + y) & ~7, stride) + (((tby + y) & 7) << 3)];
+            for (int y = 0; y < H; y++) px[y] = dv::ld_global(tcol + (dv::mul_i24((tby + y) & ~7, stride) + (((tby + y) & 7) << 3)));
         } else {
 #pragma unroll
-            for (int y = 0; y < H; y++) px[y] = d[y * stride];
+            for (int y = 0; y < H; y++) px[y] = dv::ld_global(d + y * stride);
         }
     };
 
@@ -325,6 +340,10 @@ __device__ __forceinline__ void itx_body(const DevPlanes &dst, const Dav1dHipItx
     if (COH) dv::wave_sync();
     pixel *const o = COH ? const_cast<pixel *>(pred_s) + sub * itx_tile_stride(W, H) + l : d;
     const int ostride = COH ? W : stride;
+    auto put = [&](const int y, const pixel v) {
+        if constexpr (COH) o[y * ostride] = v;
+        else dv::st_global(o + y * ostride, v);
+    };
     if (live && l < W) {
         if (dconly) {
             if (RECT2) dc = (dc * 181 + 128) >> 8;
@@ -333,24 +352,24 @@ __device__ __forceinline__ void itx_body(const DevPlanes &dst, const Dav1dHipItx
             dc = (dc * 181 + 128 + 2048) >> 12;
 #pragma unroll
             for (int y = 0; y < H; y++)
-                o[y * ostride] = ((pixel) dv::clamp3((int) dpx[y] + dc, 0, bitdepth_max));
+                put(y, (pixel) dv::clamp3((int) dpx[y] + dc, 0, bitdepth_max));
         } else {
             int out[H];
             if (TX == 0 && wht) {
                 if constexpr (H == 4) itx1d::iwht4(cin, out);
 #pragma unroll
                 for (int y = 0; y < H; y++)
-                    o[y * ostride] = ((pixel) dv::clamp3((int) dpx[y] + out[y], 0, bitdepth_max));
+                    put(y, (pixel) dv::clamp3((int) dpx[y] + out[y], 0, bitdepth_max));
             } else {
                 tx1d<H>(k2, cin, col_min, col_max, [&](const int *res) {
                     if (k2 == K_FLIPADST) {
 #pragma unroll
                         for (int y = 0; y < H; y++)
-                            o[y * ostride] = ((pixel) dv::clamp3((int) dpx[y] + ((res[H - 1 - y] + 8) >> 4), 0, bitdepth_max));
+                            put(y, (pixel) dv::clamp3((int) dpx[y] + ((res[H - 1 - y] + 8) >> 4), 0, bitdepth_max));
                     } else {
 #pragma unroll
                         for (int y = 0; y < H; y++)
-                            o[y * ostride] = ((pixel) dv::clamp3((int) dpx[y] + ((res[y] + 8) >> 4), 0, bitdepth_max));
+                            put(y, (pixel) dv::clamp3((int) dpx[y] + ((res[y] + 8) >> 4), 0, bitdepth_max));
                     }
                 });
             }
@@ -398,51 +417,64 @@ __device__ __forceinline__ void tile_write_out(const pixel *tile, const Dav1dHip
     if (direct) {
         if constexpr (OWN) {
             bpl = task_plane;
-            dv::off_to_xy(task_off, bpl == 0 ? dst.stride[0] : bpl == 1 ? dst.stride[1] : dst.stride[2], bx, by);
+            dv::off_to_xy(task_off, dv::plane_stride(dst, bpl), bx, by);
         }
     } else if (task_plane >= 0) {
         // every lane of a block's group holds the block's record: lane b takes it from the first lane of group b
         const uint32_t off = BPW == 1 ? task_off : (uint32_t) __shfl((int) task_off, (lane & (BPW - 1)) * LPBX);
         bpl = BPW == 1 ? task_plane : __shfl(task_plane, (lane & (BPW - 1)) * LPBX);
-        if (lane < nb) dv::off_to_xy(off, bpl == 0 ? dst.stride[0] : bpl == 1 ? dst.stride[1] : dst.stride[2], bx, by);
+        if (lane < nb) dv::off_to_xy(off, dv::plane_stride(dst, bpl), bx, by);
     } else if (lane < nb) {
         const Dav1dHipItxTask t = tasks[lane];
         bpl = t.plane;
-        dv::off_to_xy(t.dst_off, bpl == 0 ? dst.stride[0] : bpl == 1 ? dst.stride[1] : dst.stride[2], bx, by);
+        dv::off_to_xy(t.dst_off, dv::plane_stride(dst, bpl), bx, by);
     }
 #pragma unroll
     for (int i0 = 0; i0 < NCHK; i0 += 64) {
         const int i = i0 + lane;
         const int b = BPW == 1 ? 0 : (i / PER_BLOCK) & (BPW - 1), rem = i - (i / PER_BLOCK) * PER_BLOCK;
         const int y = rem / CPR, c = rem - y * CPR;
-        int x0, y0, pl;
-        if constexpr (BPW == 1) { x0 = __builtin_amdgcn_readfirstlane(bx); y0 = __builtin_amdgcn_readfirstlane(by); pl = __builtin_amdgcn_readfirstlane(bpl); }
-        else if (direct && OWN) { x0 = bx; y0 = by; pl = bpl; }
-        else if (direct && ONE) {
+        // The piece's plane: its row stride and where the plane and its twin begin, picked by dv::plane_stride / plane_data.  ONE: the round's
+        // plane is a scalar, so are the three; TWO: two scalar planes, and one lane select between what each of them picked.
+        int x0, y0, stride;
+        pixel *base, *tb;
+        if constexpr (BPW == 1) {
+            const int pl = __builtin_amdgcn_readfirstlane(bpl);
+            x0 = __builtin_amdgcn_readfirstlane(bx); y0 = __builtin_amdgcn_readfirstlane(by);
+            stride = dv::plane_stride(dst, pl); base = dv::plane_data<pixel>(dst, pl); tb = dv::plane_data<pixel>(twin, pl);
+        } else if (direct && OWN) {
+            x0 = bx; y0 = by;
+            stride = dv::plane_stride(dst, bpl); base = dv::plane_data<pixel>(dst, bpl); tb = dv::plane_data<pixel>(twin, bpl);
+        } else if (direct && ONE) {
             // (the record of the round's block, out of the first lane of its group in the transform body)
             const int bl = ((i0 / PER_BLOCK) & (BPW - 1)) * LPBX;
-            pl = dv::readlane(task_plane, bl);
-            dv::off_to_xy((uint32_t) dv::readlane((int) task_off, bl), pl == 0 ? dst.stride[0] : pl == 1 ? dst.stride[1] : dst.stride[2], x0, y0);
+            const int pl = dv::readlane(task_plane, bl);
+            stride = dv::plane_stride(dst, pl); base = dv::plane_data<pixel>(dst, pl); tb = dv::plane_data<pixel>(twin, pl);
+            dv::off_to_xy((uint32_t) dv::readlane((int) task_off, bl), stride, x0, y0);
         } else if (direct && TWO) {
             const int bl = ((i0 / PER_BLOCK) & (BPW - 1)) * LPBX;      // the round's first block; lanes 32 .. 63 store the next one
             const bool hi = lane >= 32;
-            pl = hi ? dv::readlane(task_plane, bl + LPBX) : dv::readlane(task_plane, bl);
+            const int pl0 = dv::readlane(task_plane, bl), pl1 = dv::readlane(task_plane, bl + LPBX);
+            const int s0 = dv::plane_stride(dst, pl0), s1 = dv::plane_stride(dst, pl1);
+            pixel *const b0 = dv::plane_data<pixel>(dst, pl0), *const b1 = dv::plane_data<pixel>(dst, pl1);
+            pixel *const t0 = dv::plane_data<pixel>(twin, pl0), *const t1 = dv::plane_data<pixel>(twin, pl1);
+            stride = hi ? s1 : s0; base = hi ? b1 : b0; tb = hi ? t1 : t0;
             const uint32_t off = (uint32_t) (hi ? dv::readlane((int) task_off, bl + LPBX) : dv::readlane((int) task_off, bl));
-            dv::off_to_xy(off, pl == 0 ? dst.stride[0] : pl == 1 ? dst.stride[1] : dst.stride[2], x0, y0);
-        } else { x0 = __shfl(bx, b); y0 = __shfl(by, b); pl = __shfl(bpl, b); }
+            dv::off_to_xy(off, stride, x0, y0);
+        } else {
+            x0 = __shfl(bx, b); y0 = __shfl(by, b);
+            const int pl = __shfl(bpl, b);
+            stride = dv::plane_stride(dst, pl); base = dv::plane_data<pixel>(dst, pl); tb = dv::plane_data<pixel>(twin, pl);
+        }
         if (i >= NCHK || i / PER_BLOCK >= nb) continue;
         const piece_t v = *reinterpret_cast<const piece_t *>(tile + b * itx_tile_stride(W, H) + y * W + c * CP);
 #ifdef DV_KO_WRITE
         if (*reinterpret_cast<const uint32_t *>(&v) != 0xfeedbeefu) continue;
 #endif
         const int X = x0 + c * CP, Y = y0 + y;
-        const int stride = pl == 0 ? dst.stride[0] : pl == 1 ? dst.stride[1] : dst.stride[2];
-        pixel *const base = reinterpret_cast<pixel *>(pl == 0 ? dst.data[0] : pl == 1 ? dst.data[1] : dst.data[2]);
-        if (raster) *reinterpret_cast<piece_t *>(base + (dv::mul_i24(Y, stride) + X)) = v;
-        if (has_twin) {      // (kernel arguments are never indexed by a run-time value nor have their address taken: either sends them to scratch memory)
-            pixel *const tb = reinterpret_cast<pixel *>(pl == 0 ? twin.data[0] : pl == 1 ? twin.data[1] : twin.data[2]);
-            *reinterpret_cast<piece_t *>(tb + (dv::mul_i24(Y & ~7, stride) + ((X >> 3) << 6) + ((Y & 7) << 3) + (X & 7))) = v;
-        }
+        // (the planes are global memory whatever the selects above make of the pointers: dv::st_global)
+        if (raster) dv::st_global(reinterpret_cast<piece_t *>(base + (dv::mul_i24(Y, stride) + X)), v);
+        if (has_twin) dv::st_global(reinterpret_cast<piece_t *>(tb + (dv::mul_i24(Y & ~7, stride) + ((X >> 3) << 6) + ((Y & 7) << 3) + (X & 7))), v);
     }
 }
 

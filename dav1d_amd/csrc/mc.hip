@@ -42,7 +42,7 @@ namespace {
 #define MC_WAVES 1
 #endif
 template <int TW, int TH, typename pixel, bool TILED>
-__global__ __launch_bounds__(64 * MC_WAVES) void mc_kernel(const DevPlanes dst, const RefSet refs, const McTile *__restrict__ tiles,
+__global__ __launch_bounds__(64 * MC_WAVES) void mc_kernel(const DevPlanes dst, const RefSet refs, const int n_refs, const McTile *__restrict__ tiles,
                                                 const int n, int16_t *__restrict__ prep, const int bitdepth_max)
 {
     constexpr int G = 64 / mc_cmin(64, TW * TH / 4);
@@ -51,19 +51,19 @@ __global__ __launch_bounds__(64 * MC_WAVES) void mc_kernel(const DevPlanes dst, 
     const int wv = MC_WAVES == 1 ? 0 : __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
     const int t0 = ((int) dv::xcd_chunk_id(blockIdx.x, gridDim.x) * MC_WAVES + wv) * G;
     if (t0 >= n) return;
-    mc_body<TW, TH, pixel, false, TILED>(dst, refs, tiles, t0, dv::imin(G, n - t0), prep, bitdepth_max, smem[wv]);
+    mc_body<TW, TH, pixel, false, TILED>(dst, refs, n_refs, tiles, t0, dv::imin(G, n - t0), prep, bitdepth_max, smem[wv]);
 }
 
 // TILED references and the picture's own tiled twin written along with the raster planes (mc_body.h, TWIN)
 template <int TW, int TH, typename pixel>
-__global__ __launch_bounds__(64) void mc_twin_kernel(const DevPlanes dst, const RefSet refs, const McTile *__restrict__ tiles,
+__global__ __launch_bounds__(64) void mc_twin_kernel(const DevPlanes dst, const RefSet refs, const int n_refs, const McTile *__restrict__ tiles,
                                                      const int n, int16_t *__restrict__ prep, const int bitdepth_max, const DevPlanes twin)
 {
     constexpr int G = 64 / mc_cmin(64, TW * TH / 4);
     __shared__ uint4 smem[(mc_lds_bytes<TW, TH, true>() + 15) / 16];
     const int t0 = (int) dv::xcd_chunk_id(blockIdx.x, gridDim.x) * G;
     if (t0 >= n) return;
-    mc_body<TW, TH, pixel, false, true, true>(dst, refs, tiles, t0, dv::imin(G, n - t0), prep, bitdepth_max, smem, nullptr, 0, 0, 0, 0, twin);
+    mc_body<TW, TH, pixel, false, true, true>(dst, refs, n_refs, tiles, t0, dv::imin(G, n - t0), prep, bitdepth_max, smem, nullptr, 0, 0, 0, 0, twin);
 }
 
 // every tile shape in one launch: the tiles are ordered by where they read (all shapes interleaved, see
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(64) void mc_all_kernel(const DevPlanes dst, const R
     if (gi >= n_groups) return;
     const McGroup g = groups[__builtin_amdgcn_readfirstlane(gi)];
     const int t0 = __builtin_amdgcn_readfirstlane((int) g.start), nt = __builtin_amdgcn_readfirstlane((int) g.n);
-#define CASE(C, TW, TH) case C: mc_body<TW, TH, pixel>(dst, refs, tiles, t0, nt, prep, bitdepth_max, smem); break;
+#define CASE(C, TW, TH) case C: mc_body<TW, TH, pixel>(dst, refs, 8, tiles, t0, nt, prep, bitdepth_max, smem); break;
     const int cls = __builtin_amdgcn_readfirstlane((int) g.cls);
     if (SMALL && cls < 6) {
         switch (cls) {
@@ -106,14 +106,14 @@ __global__ __launch_bounds__(64) void mc_all_kernel(const DevPlanes dst, const R
 }
 
 template <typename pixel, bool TILED>
-hipError_t launch_cls(const int cls, const DevPlanes &dst, const RefSet &refs, const McTile *tiles, const int n,
+hipError_t launch_cls(const int cls, const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *tiles, const int n,
                       int16_t *prep, const int bitdepth_max, hipStream_t stream)
 {
 #define CASE(C, TW, TH) case C: { \
         constexpr int lpt = mc_cmin(64, TW * TH / 4); \
         constexpr int g = 64 / lpt; \
         hipLaunchKernelGGL((mc_kernel<TW, TH, pixel, TILED>), dim3(((n + g - 1) / g + MC_WAVES - 1) / MC_WAVES), dim3(64 * MC_WAVES), 0, stream, \
-                           dst, refs, tiles, n, prep, bitdepth_max); \
+                           dst, refs, n_refs, tiles, n, prep, bitdepth_max); \
         break; }
     // class = 3 * wclass + hclass, widths 4 8 16 32 64, heights 4 8 16
     switch (cls) {
@@ -129,14 +129,14 @@ hipError_t launch_cls(const int cls, const DevPlanes &dst, const RefSet &refs, c
 }
 
 template <typename pixel>
-hipError_t launch_cls_twin(const int cls, const DevPlanes &dst, const RefSet &refs, const McTile *tiles, const int n,
+hipError_t launch_cls_twin(const int cls, const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *tiles, const int n,
                            int16_t *prep, const int bitdepth_max, const DevPlanes &twin, hipStream_t stream)
 {
 #define CASE(C, TW, TH) case C: { \
         constexpr int lpt = mc_cmin(64, TW * TH / 4); \
         constexpr int g = 64 / lpt; \
         hipLaunchKernelGGL((mc_twin_kernel<TW, TH, pixel>), dim3((n + g - 1) / g), dim3(64), 0, stream, \
-                           dst, refs, tiles, n, prep, bitdepth_max, twin); \
+                           dst, refs, n_refs, tiles, n, prep, bitdepth_max, twin); \
         break; }
     switch (cls) {
         CASE(0, 4, 4) CASE(1, 4, 8) CASE(2, 4, 16)
@@ -165,10 +165,10 @@ extern "C" int dav1d_hip_launch_mc_bin_twin(const DevPlanes *dst, const DevPlane
 #ifdef DV_LEAN
     if (bpc == 8) return -ENOTSUP;
 #else
-    if (bpc == 8) e = launch_cls_twin<uint8_t>(cls, *dst, rs, tiles, n, prep, bitdepth_max, *dst_twin, (hipStream_t) stream);
+    if (bpc == 8) e = launch_cls_twin<uint8_t>(cls, *dst, rs, n_refs, tiles, n, prep, bitdepth_max, *dst_twin, (hipStream_t) stream);
     else
 #endif
-                  e = launch_cls_twin<uint16_t>(cls, *dst, rs, tiles, n, prep, bitdepth_max, *dst_twin, (hipStream_t) stream);
+                  e = launch_cls_twin<uint16_t>(cls, *dst, rs, n_refs, tiles, n, prep, bitdepth_max, *dst_twin, (hipStream_t) stream);
     return hip_rc(e);
 }
 
@@ -188,10 +188,10 @@ extern "C" int dav1d_hip_launch_mc_bin(const DevPlanes *dst, const DevPlanes *re
     return -ENOTSUP;
 #else
     hipError_t e;
-    if (bpc == 8) e = tiled ? launch_cls<uint8_t, true>(cls, *dst, rs, tiles, n, prep, bitdepth_max, (hipStream_t) stream)
-                            : launch_cls<uint8_t, false>(cls, *dst, rs, tiles, n, prep, bitdepth_max, (hipStream_t) stream);
-    else          e = tiled ? launch_cls<uint16_t, true>(cls, *dst, rs, tiles, n, prep, bitdepth_max, (hipStream_t) stream)
-                            : launch_cls<uint16_t, false>(cls, *dst, rs, tiles, n, prep, bitdepth_max, (hipStream_t) stream);
+    if (bpc == 8) e = tiled ? launch_cls<uint8_t, true>(cls, *dst, rs, n_refs, tiles, n, prep, bitdepth_max, (hipStream_t) stream)
+                            : launch_cls<uint8_t, false>(cls, *dst, rs, n_refs, tiles, n, prep, bitdepth_max, (hipStream_t) stream);
+    else          e = tiled ? launch_cls<uint16_t, true>(cls, *dst, rs, n_refs, tiles, n, prep, bitdepth_max, (hipStream_t) stream)
+                            : launch_cls<uint16_t, false>(cls, *dst, rs, n_refs, tiles, n, prep, bitdepth_max, (hipStream_t) stream);
     return hip_rc(e);
 #endif
 }

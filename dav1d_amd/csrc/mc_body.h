@@ -41,6 +41,9 @@ __device__ __forceinline__ Taps load_taps(const int set, const int m) {
 }
 
 constexpr int mc_cmin(int a, int b) { return a < b ? a : b; }
+#ifndef MC_FRESH_MIN_TW
+#define MC_FRESH_MIN_TW 8      // (narrowest tile whose paired form works the lane's values out again in every call, see mc_body: the 4x4 pairs make ONE call)
+#endif
 // window row stride in pixels: TW + 8 columns rounded up to whole 16-byte chunks.  4-wide tiles: blocks of width 4 are only ever
 // filtered with the 4-tap sets, bilinear or the unit tap (reference src/mc_tmpl.c GET_H_FILTER: w > 4 ? type : 3 + (type & 1);
 // the host builds the tiles by the same rule, api_lists.hip), whose taps 0, 1, 6 and 7 are zero: the 4 outputs of a row reach the 7
@@ -155,7 +158,7 @@ __device__ __forceinline__ void mc_gather(const McRef rf, const McPred &pd, cons
 #ifdef DV_KO_GATHER      // (knock-out variant builds, tools/knockout.sh: timing only, the pixels are wrong)
                     if (ok[ri][pi]) { ld[ri][pi].x = (unsigned) (size_t) prow; ld[ri][pi].y = (unsigned) x; if constexpr (HBD) { ld[ri][pi].z = 0; ld[ri][pi].w = 1; } }
 #else
-                    if (ok[ri][pi]) ld[ri][pi] = *reinterpret_cast<const piece_t *>(prow + (x << 3));
+                    if (ok[ri][pi]) ld[ri][pi] = dv::ld_global(reinterpret_cast<const piece_t *>(prow + (x << 3)));
 #endif
                 }
             }
@@ -182,7 +185,7 @@ __device__ __forceinline__ void mc_gather(const McRef rf, const McPred &pd, cons
                     const int wq = dv::div_small<WS>(i), wr = WR0 + wq;
                     const int sy = dv::iclip(y0 + wr, 0, rh - 1);
                     const int sx = dv::iclip(xa + (i - wq * WS), 0, rw - 1);
-                    v[e] = src[dv::mul_i24(sy & ~7, rs) + ((sx >> 3) << 6) + ((sy & 7) << 3) + (sx & 7)];
+                    v[e] = dv::ld_global(src + (dv::mul_i24(sy & ~7, rs) + ((sx >> 3) << 6) + ((sy & 7) << 3) + (sx & 7)));
                 }
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
@@ -207,10 +210,10 @@ __device__ __forceinline__ void mc_gather(const McRef rf, const McPred &pd, cons
             ld[k] = make_uint4(0, 0, 0, 0);
             if (wr < row_lo || wr >= row_hi) continue;
             if (HBD) {
-                const U128u v = *reinterpret_cast<const U128u *>(p);
+                const U128u v = dv::ld_global(reinterpret_cast<const U128u *>(p));
                 ld[k] = make_uint4(v.a, v.b, v.c, v.d);
             } else {
-                const U64b v = *reinterpret_cast<const U64b *>(p);
+                const U64b v = dv::ld_global(reinterpret_cast<const U64b *>(p));
                 // bytes -> 16-bit lanes: one byte permute per pair of pixels (selector 0x0c = a zero byte)
                 ld[k] = make_uint4(__builtin_amdgcn_perm(0u, v.a, 0x0c010c00u), __builtin_amdgcn_perm(0u, v.a, 0x0c030c02u),
                                    __builtin_amdgcn_perm(0u, v.b, 0x0c010c00u), __builtin_amdgcn_perm(0u, v.b, 0x0c030c02u));
@@ -238,7 +241,7 @@ __device__ __forceinline__ void mc_gather(const McRef rf, const McPred &pd, cons
                 const int i = dv::imin(i0 + e * LPT, WRG * WS - 1);
                 const int sy = dv::iclip(y0 + WR0 + i / WS, 0, rh - 1);
                 const int sx = dv::iclip(x0 + i % WS, 0, rw - 1);
-                v[e] = src[sy * rs + sx];
+                v[e] = dv::ld_global(src + (sy * rs + sx));
             }
 #pragma unroll
             for (int e = 0; e < 8; e++) {
@@ -415,7 +418,7 @@ __device__ __forceinline__ void mc_vpass(const McPred &pd, const Taps &fv, const
 // TWIN: pixels that go to the picture (PUT / AVG / WAVG tiles outside the paired kernels) go to the planes of its tiled twin as well
 // (`twin`: same strides; every 4-pixel strip lies inside one tile row).
 template <int TW, int TH, typename pixel, bool TO_LDS = false, bool TILED = false, bool TWIN = false>
-__device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs, const McTile *__restrict__ tiles, const int t0, const int nt,
+__device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *__restrict__ tiles, const int t0, const int nt,
                                         int16_t *__restrict__ prep, const int bitdepth_max, uint4 *smem,
                                         pixel *pred_s = nullptr, const int pred_tile0 = 0, const int pred_tpb_log2 = 0,
                                         const int pred_w = 0, const int pred_h = 0, const DevPlanes &twin = DevPlanes())
@@ -444,7 +447,11 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
     constexpr int SL = TH == 4 ? TW : 0;                // 4-row tiles: one pair of slack in front of and behind the intermediates
     uint32_t *const mid_s = reinterpret_cast<uint32_t *>(win_s + (WR0 + G * WRA) * WS) + SL;
 
-    const int lane = dv::lane_id();       // the body belongs to one wave (recon.hip runs several side by side in a workgroup)
+    // the body belongs to one wave (recon.hip runs several side by side in a workgroup).  TO_LDS: the paired kernels call this body up to
+    // four times in a loop; everything that only depends on the lane was computed once in front of that loop and stayed in registers through
+    // all of the wave — at the 72 registers of seven waves per SIMD that was what spilled (8x8 pairs: 16 bytes per lane).  dv::fresh: worked
+    // out again in every call, a handful of integer operations.
+    const int lane = TO_LDS && TW >= MC_FRESH_MIN_TW ? dv::fresh(dv::lane_id()) : dv::lane_id();
     // G == 1: the whole wave works on one tile, so the record, the taps and all the control flow
     // derived from them are wave-uniform (scalar loads, SGPRs, s_cbranch instead of exec masking)
     const int sub = G == 1 ? 0 : lane / LPT, l = G == 1 ? lane : lane % LPT;
@@ -465,9 +472,12 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
         // the reference plane table goes to LDS in the same round trip: the lanes index it by their own tile's reference,
         // and a second, dependent trip to the kernel arguments would sit in front of every window fetch
         uint32_t *const ref_s = mid_s + G * NPRA * TW + SL;
+        // (only the n_refs entries the call has: no record names another — the callers check — and the table's other slots are never read)
         const uint32_t *rsrc = reinterpret_cast<const uint32_t *>(&refs);
+        const int nrw = n_refs * (int) (sizeof(DevPlanes) / 4);
 #pragma unroll
-        for (int i = 0; i < (int) sizeof(RefSet) / 4; i += 64) ref_s[i + lane] = rsrc[i + lane];
+        for (int i = 0; i < (int) sizeof(RefSet) / 4; i += 64)
+            if (i + lane < nrw) ref_s[i + lane] = rsrc[i + lane];
         dv::wave_sync();
         const uint32_t *rp = rec_s + (live ? sub : 0) * RW;
         uint32_t *tw_ = reinterpret_cast<uint32_t *>(&t);
@@ -555,7 +565,26 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
 
     // ---- combine + store
     int tbx = 0, tby = 0;          // TWIN: the block's position in its plane
-    const int tstride = t.plane == 0 ? dst.stride[0] : t.plane == 1 ? dst.stride[1] : dst.stride[2];
+    const int tstride = dv::plane_stride(dst, t.plane);
+    // a strip of four pixels (or its first nvalid) to global memory — the picture, its twin, the scratch arena — or to the LDS tile of the
+    // paired kernels: told apart HERE, not by a select between the pointers, which would make every one of these stores a flat one
+    auto put_strip = [&](pixel *const p, const int (&o)[4], const int nvalid, const auto global) {
+        if (nvalid == 4) {
+            if constexpr (HBD) {
+                const uint2 v = make_uint2(dv::pack2(o[0], o[1]), dv::pack2(o[2], o[3]));
+                if constexpr (decltype(global)::value) dv::st_global(reinterpret_cast<uint2 *>(p), v); else *reinterpret_cast<uint2 *>(p) = v;
+            } else {
+                const uint32_t v = (uint32_t) o[0] | ((uint32_t) o[1] << 8) | ((uint32_t) o[2] << 16) | ((uint32_t) o[3] << 24);
+                if constexpr (decltype(global)::value) dv::st_global(reinterpret_cast<uint32_t *>(p), v); else *reinterpret_cast<uint32_t *>(p) = v;
+            }
+        } else {
+#pragma unroll
+            for (int x = 0; x < 3; x++) {        // (nvalid < 4.  Unrolled: as a loop it keeps 64-bit counters and addresses alive across the whole body)
+                if (x >= nvalid) continue;
+                if constexpr (decltype(global)::value) dv::st_global(p + x, (pixel) o[x]); else p[x] = (pixel) o[x];
+            }
+        }
+    };
     if (TWIN && live && t.kind != MCT_PREP && t.kind != MCT_PUT_TMP) dv::off_to_xy(t.dst_off, tstride, tbx, tby);
     if (live) {
 #pragma unroll
@@ -580,28 +609,17 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
 #pragma unroll
                 for (int x = 0; x < 4; x++) o[x] = dv::clamp3(o[x], 0, bitdepth_max);
                 // PUT_TMP: pixels into the scratch arena, row stride = block width (the reference's `lap` buffer of obmc())
-                pixel *d = t.kind == MCT_PUT_TMP
-                    ? reinterpret_cast<pixel *>(prep) + t.dst_off + (t.oy + vr) * t.bw + t.ox + 4 * vs
-                    : TO_LDS ? pred_s + ((ti - pred_tile0) >> pred_tpb_log2) * (pred_w * (pred_h + 1)) + (t.oy + vr) * pred_w + t.ox + 4 * vs
-                    : reinterpret_cast<pixel *>(dst.data[t.plane]) + t.dst_off + (t.oy + vr) * dst.stride[t.plane] + t.ox + 4 * vs;
                 // TWIN with twin.tiled == 2: the picture lives in its twin only (DAV1D_HIP_TWIN_ONLY) — nothing goes to the raster planes
-                const bool to_raster = !(TWIN && !TO_LDS && twin.tiled == 2 && t.kind != MCT_PUT_TMP);
-                if (!to_raster) {
-                } else if (nvalid == 4) {
-                    if (HBD) *reinterpret_cast<uint2 *>(d) = make_uint2(dv::pack2(o[0], o[1]), dv::pack2(o[2], o[3]));
-                    else *reinterpret_cast<uint32_t *>(d) = (uint32_t) o[0] | ((uint32_t) o[1] << 8) | ((uint32_t) o[2] << 16) | ((uint32_t) o[3] << 24);
-                } else if (nvalid > 0) {
-                    for (int x = 0; x < nvalid; x++) d[x] = (pixel) o[x];
-                }
-                if (TWIN && !TO_LDS && t.kind != MCT_PUT_TMP && nvalid > 0) {
-                    const int X = tbx + t.ox + 4 * vs, Y = tby + t.oy + vr;
-                    pixel *const td = reinterpret_cast<pixel *>(t.plane == 0 ? twin.data[0] : t.plane == 1 ? twin.data[1] : twin.data[2]) +
-                                      (dv::mul_i24(Y & ~7, tstride) + ((X >> 3) << 6) + ((Y & 7) << 3) + (X & 7));
-                    if (nvalid == 4) {
-                        if (HBD) *reinterpret_cast<uint2 *>(td) = make_uint2(dv::pack2(o[0], o[1]), dv::pack2(o[2], o[3]));
-                        else *reinterpret_cast<uint32_t *>(td) = (uint32_t) o[0] | ((uint32_t) o[1] << 8) | ((uint32_t) o[2] << 16) | ((uint32_t) o[3] << 24);
-                    } else {
-                        for (int x = 0; x < nvalid; x++) td[x] = (pixel) o[x];
+                if (t.kind == MCT_PUT_TMP) {
+                    put_strip(reinterpret_cast<pixel *>(prep) + t.dst_off + (t.oy + vr) * t.bw + t.ox + 4 * vs, o, nvalid, std::true_type());
+                } else if constexpr (TO_LDS) {
+                    put_strip(pred_s + ((ti - pred_tile0) >> pred_tpb_log2) * (pred_w * (pred_h + 1)) + (t.oy + vr) * pred_w + t.ox + 4 * vs, o, nvalid, std::false_type());
+                } else {
+                    if (!(TWIN && twin.tiled == 2))
+                        put_strip(dv::plane_data<pixel>(dst, t.plane) + t.dst_off + (t.oy + vr) * tstride + t.ox + 4 * vs, o, nvalid, std::true_type());
+                    if (TWIN && nvalid > 0) {
+                        const int X = tbx + t.ox + 4 * vs, Y = tby + t.oy + vr;
+                        put_strip(dv::plane_data<pixel>(twin, t.plane) + (dv::mul_i24(Y & ~7, tstride) + ((X >> 3) << 6) + ((Y & 7) << 3) + (X & 7)), o, nvalid, std::true_type());
                     }
                 }
             } else {

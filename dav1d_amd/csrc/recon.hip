@@ -25,7 +25,7 @@ namespace {
 #define RECON_WAVES_8 7
 #endif
 #ifndef RECON_WAVES_32
-#define RECON_WAVES_32 7   // (the 32x32 pairs: 90 registers whatever is asked, and the LDS holds 4.5 waves per SIMD)
+#define RECON_WAVES_32 5   // (the 32x32 pairs: the LDS holds 4.5 waves per SIMD; asked for 7 the allocator gives up on 72 registers and takes 90, asked for 5: 85)
 #endif
 
 constexpr int rc_log2(int v) { return v <= 1 ? 0 : 1 + rc_log2(v >> 1); }
@@ -48,7 +48,7 @@ template <int CLS> constexpr int recon_waves() {
 // two bytes per lane and row — and go to the picture's tiled twin as well when `twin` has planes (twin.data[0] != nullptr).
 template <int CLS, typename pixel, typename coef, bool COOP, bool TILED, bool WIDE>
 __global__ __launch_bounds__(COOP ? 64 * recon_waves<CLS>() : 64, COOP ? 1 : CLS == 1 ? RECON_WAVES_8 : CLS == 3 ? RECON_WAVES_32 : RECON_WAVES)
-void recon_fused_kernel(const DevPlanes dst, const RefSet refs, const McTile *__restrict__ tiles,
+void recon_fused_kernel(const DevPlanes dst, const RefSet refs, const int n_refs, const McTile *__restrict__ tiles,
                         const Dav1dHipItxTask *__restrict__ tasks, const int n_blocks,
                         int16_t *__restrict__ prep, coef *__restrict__ cf, const int bitdepth_max, const DevPlanes twin)
 {
@@ -85,14 +85,14 @@ void recon_fused_kernel(const DevPlanes dst, const RefSet refs, const McTile *__
 #endif
     if constexpr (NW == 1) {
         for (int c = 0; c < ntile; c += G) {
-            mc_body<TW, TH, pixel, true, TILED>(dst, refs, tiles, tile0 + c, dv::imin(G, ntile - c), prep, bitdepth_max, smem_mc,
+            mc_body<TW, TH, pixel, true, TILED>(dst, refs, n_refs, tiles, tile0 + c, dv::imin(G, ntile - c), prep, bitdepth_max, smem_mc,
                                          pred, tile0, rc_log2(TPB), W, W);
             dv::wave_sync();
         }
     } else {
         const int c = wave * G;
         if (c < ntile)
-            mc_body<TW, TH, pixel, true, TILED>(dst, refs, tiles, tile0 + c, dv::imin(G, ntile - c), prep, bitdepth_max, smem_mc,
+            mc_body<TW, TH, pixel, true, TILED>(dst, refs, n_refs, tiles, tile0 + c, dv::imin(G, ntile - c), prep, bitdepth_max, smem_mc,
                                          pred, tile0, rc_log2(TPB), W, W);
         __syncthreads();
         if (wave) return;
@@ -104,7 +104,7 @@ void recon_fused_kernel(const DevPlanes dst, const RefSet refs, const McTile *__
 #ifdef DV_KO_NOITX
         if (bitdepth_max == 12345)
 #endif
-        itx_body<TX, pixel, coef, true, true>(dst, tasks, n_blocks, cf, bitdepth_max, group, smem_itx, pred, false, &toff, &tpl);
+        itx_body<TX, pixel, coef, true, true, false, true>(dst, tasks, n_blocks, cf, bitdepth_max, group, smem_itx, pred, false, &toff, &tpl);
         dv::wave_sync();
         DV_PHASE(768 + CLS * 16 + 1);
 #ifdef DV_KO_NOOUT
@@ -113,14 +113,14 @@ void recon_fused_kernel(const DevPlanes dst, const RefSet refs, const McTile *__
         tile_write_out<W, W, BPW, pixel>(pred, tasks + block0, nb, dst, twin, twin.data[0] != nullptr, twin.tiled != 2, toff, tpl);
         DV_PHASE(768 + CLS * 16 + 2);
     } else {
-        itx_body<TX, pixel, coef, true>(dst, tasks, n_blocks, cf, bitdepth_max, group, smem_itx, pred);
+        itx_body<TX, pixel, coef, true, false, false, true>(dst, tasks, n_blocks, cf, bitdepth_max, group, smem_itx, pred);
         DV_PHASE(768 + CLS * 16 + 1);
     }
     DV_PHASE_WAVE(768 + CLS * 16 + 3);
 }
 
 template <int CLS, typename pixel, typename coef, bool TILED, bool WIDE>
-void launch_cls(const DevPlanes &dst, const RefSet &refs, const McTile *tiles, const Dav1dHipItxTask *tasks, const int n,
+void launch_cls(const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *tiles, const Dav1dHipItxTask *tasks, const int n,
                 int16_t *prep, coef *cf, const int bitdepth_max, const int coop_below, const DevPlanes &twin, hipStream_t stream)
 {
     constexpr int W = 4 << CLS, LPB = cmax(cmin(W, 32), W), BPW = 64 / LPB;
@@ -128,42 +128,42 @@ void launch_cls(const DevPlanes &dst, const RefSet &refs, const McTile *tiles, c
 #ifndef DV_LEAN      // (DV_LEAN: variant builds of tools/build_variant.py that only hold what the 10-bit tiled step launches — a tenth of the compile time)
     if (recon_waves<CLS>() > 1 && groups < coop_below)
         hipLaunchKernelGGL((recon_fused_kernel<CLS, pixel, coef, true, TILED, WIDE>), dim3(groups), dim3(64 * recon_waves<CLS>()), 0, stream,
-                           dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, twin);
+                           dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, twin);
     else
 #endif
         hipLaunchKernelGGL((recon_fused_kernel<CLS, pixel, coef, false, TILED, WIDE>), dim3(groups), dim3(64), 0, stream,
-                           dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, twin);
+                           dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, twin);
 }
 
 template <typename pixel, typename coef, bool TILED, bool WIDE>
-hipError_t launch_any(const int cls, const DevPlanes &dst, const RefSet &refs, const McTile *tiles, const Dav1dHipItxTask *tasks,
+hipError_t launch_any(const int cls, const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *tiles, const Dav1dHipItxTask *tasks,
                       const int n, int16_t *prep, coef *cf, const int bitdepth_max, const int coop_below, const DevPlanes &twin, hipStream_t stream)
 {
     switch (cls) {
-    case 0: launch_cls<0, pixel, coef, TILED, WIDE>(dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
-    case 1: launch_cls<1, pixel, coef, TILED, WIDE>(dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
-    case 2: launch_cls<2, pixel, coef, TILED, WIDE>(dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
-    case 3: launch_cls<3, pixel, coef, TILED, WIDE>(dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
-    case 4: launch_cls<4, pixel, coef, TILED, WIDE>(dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
+    case 0: launch_cls<0, pixel, coef, TILED, WIDE>(dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
+    case 1: launch_cls<1, pixel, coef, TILED, WIDE>(dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
+    case 2: launch_cls<2, pixel, coef, TILED, WIDE>(dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
+    case 3: launch_cls<3, pixel, coef, TILED, WIDE>(dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
+    case 4: launch_cls<4, pixel, coef, TILED, WIDE>(dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, stream); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
 template <typename pixel, typename coef>
-hipError_t launch_variant(const bool tiled, const bool wide, const int cls, const DevPlanes &dst, const RefSet &refs, const McTile *tiles,
+hipError_t launch_variant(const bool tiled, const bool wide, const int cls, const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *tiles,
                           const Dav1dHipItxTask *tasks, const int n, int16_t *prep, coef *cf, const int bitdepth_max, const int coop_below,
                           const DevPlanes &twin, hipStream_t st)
 {
 #ifdef DV_LEAN
     if (!tiled || !wide || sizeof(pixel) != 2) return hipErrorInvalidValue;
-    if constexpr (sizeof(pixel) == 2) return launch_any<pixel, coef, true, true>(cls, dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st);
+    if constexpr (sizeof(pixel) == 2) return launch_any<pixel, coef, true, true>(cls, dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st);
     else return hipErrorInvalidValue;
 #else
-    if (tiled) return wide ? launch_any<pixel, coef, true, true>(cls, dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st)
-                           : launch_any<pixel, coef, true, false>(cls, dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st);
-    return wide ? launch_any<pixel, coef, false, true>(cls, dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st)
-                : launch_any<pixel, coef, false, false>(cls, dst, refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st);
+    if (tiled) return wide ? launch_any<pixel, coef, true, true>(cls, dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st)
+                           : launch_any<pixel, coef, true, false>(cls, dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st);
+    return wide ? launch_any<pixel, coef, false, true>(cls, dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st)
+                : launch_any<pixel, coef, false, false>(cls, dst, refs, n_refs, tiles, tasks, n, prep, cf, bitdepth_max, coop_below, twin, st);
 #endif
 }
 
@@ -189,8 +189,8 @@ extern "C" int dav1d_hip_launch_recon_fused_out(const DevPlanes *dst, const DevP
     if (dst_twin) twin = *dst_twin;
     hipStream_t st = (hipStream_t) stream;
     hipError_t e;
-    if (bpc == 8) e = launch_variant<uint8_t, int16_t>(tiled, wide & 1, cls, *dst, rs, tiles, tasks, n, prep, (int16_t *) coef, bitdepth_max, coop_below, twin, st);
-    else          e = launch_variant<uint16_t, int32_t>(tiled, wide & 1, cls, *dst, rs, tiles, tasks, n, prep, (int32_t *) coef, bitdepth_max, coop_below, twin, st);
+    if (bpc == 8) e = launch_variant<uint8_t, int16_t>(tiled, wide & 1, cls, *dst, rs, n_refs, tiles, tasks, n, prep, (int16_t *) coef, bitdepth_max, coop_below, twin, st);
+    else          e = launch_variant<uint16_t, int32_t>(tiled, wide & 1, cls, *dst, rs, n_refs, tiles, tasks, n, prep, (int32_t *) coef, bitdepth_max, coop_below, twin, st);
     return hip_rc(e);
 }
 

@@ -16,8 +16,11 @@ for l in lines[start:end]:
         c[m.group(1)] += 1
 cls = collections.Counter()
 for k, v in c.items():
+    # flat_* (a pointer the compiler could not place: issued to the LDS path as well, counted in lgkmcnt and vmcnt) and scratch_* (private
+    # memory: spills, or a kernel argument copied to be indexed) are classes of their own: either is a finding in these kernels
     cls["VALU" if k.startswith("v_") else "SALU" if k.startswith("s_") else "LDS" if k.startswith("ds_") else
-        "VMEM" if k.startswith(("global_", "buffer_", "flat_", "scratch_")) else "other"] += v
+        "FLAT" if k.startswith("flat_") else "SCRATCH" if k.startswith("scratch_") else
+        "VMEM" if k.startswith(("global_", "buffer_")) else "other"] += v
 print(sum(c.values()), dict(cls))
 for k, v in c.most_common(int(sys.argv[3]) if len(sys.argv) > 3 else 40):
     print("%5d %s" % (v, k))
