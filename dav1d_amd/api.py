@@ -18,7 +18,8 @@ SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR, SURFACE_RGB_PACKED, SURF
 SAMPLE_NATIVE, SAMPLE_MSB16, SAMPLE_F32, SAMPLE_F16 = 0, 1, 2, 3      # enum Dav1dHipSurfaceSample
 CHROMA_REPLICATE, CHROMA_VERTICAL, CHROMA_COLOCATED = 0, 1, 2         # Dav1dHipRgbParams.chroma_pos
 RESIZE_BILINEAR = 0                                                   # enum Dav1dHipResizeFilter
-_INTERP = {"bilinear": RESIZE_BILINEAR}                               # export_to_tensor / export_batch_to_tensor: interp=
+_INTERP = {"bilinear": RESIZE_BILINEAR, "area": RESIZE_BILINEAR}      # export_to_tensor / export_batch_to_tensor: interp= ("area": the reduced calls, an
+                                                                      # axis that goes up is interpolated linearly there as well)
 
 
 def _filter_of(interp):
@@ -215,6 +216,21 @@ class DevicePicture:
         _chk(min(n, 0), "surface_rgb_resized_rows_needed")
         return n
 
+    def export_rgb_reduced(self, surface, crop=None, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_reduced: export_rgb_resized whose axes may go down by any ratio up to 256:1 (thumbnails, network inputs from
+        8K pictures): the area rule at every ratio, `filter` for an axis that goes up.  Up to 8:1 on every axis the bytes are export_rgb_resized's.
+        Asynchronous like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_reduced(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), int(filter),
+                                                               row0, row1), "surface_export_rgb_reduced")
+
+    def rgb_reduced_rows_needed(self, surface, crop, chroma_pos, row1, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_rgb_reduced_rows_needed: the source luma rows, from the top, that destination rows [0, row1) of export_rgb_reduced read"""
+        p = self._rgb_params(chroma_pos, None, None)
+        n = self.ctx.lib.dav1d_hip_surface_rgb_reduced_rows_needed(C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), int(filter), row1)
+        _chk(min(n, 0), "surface_rgb_reduced_rows_needed")
+        return n
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -321,7 +337,9 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     `colour` (a handle of Context.colour / Context.colour_for): float RGB tensors go through DevicePicture.export_rgb_colour; not together with
     `grain`, `crop` or `resize`.
     `interp="bilinear"` (with `resize=True`; RGB tensors only, no `grain`, no `colour`): the output may be LARGER than the crop on either axis; the
-    call goes through DevicePicture.export_rgb_resized.  `interp=None` keeps the routes above, which refuse such a size."""
+    call goes through DevicePicture.export_rgb_resized.  `interp="area"`: through DevicePicture.export_rgb_reduced, which also serves an output up to
+    256 times SMALLER than the crop on either axis (an axis that goes up is interpolated linearly).  `interp=None` keeps the routes above, which
+    refuse such sizes."""
     import torch
     if interp is not None:
         flt = _filter_of(interp)
@@ -373,6 +391,9 @@ def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range
     s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range)
     if s.dtype.itemsize != es or (not packed and [tuple(t.shape[-2:]) for t in ts] != s.shapes[:len(ts)]):
         raise ValueError("tensor shapes / dtype do not fit the surface: %s %s" % (s.shapes, s.dtype))
+    if interp == "area":
+        pic.export_rgb_reduced(s, crop, chroma_pos or 0, scale, bias, row0, row1, flt)
+        return s
     if interp is not None:
         pic.export_rgb_resized(s, crop, chroma_pos or 0, scale, bias, row0, row1, flt)
         return s
@@ -399,7 +420,8 @@ def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sam
     export_to_tensor (float32: F32, float16: F16, else `sample`, native by default).  Item k is written through tensor[k]: any batch stride is fine
     (a view such as big[::2]), rows need unit stride.  ValueError for what export_to_tensor raises, for len(pics) != N, and for a shape
     (N, 3, n, 3) or (N, 3, n, 4), which reads both ways.  `interp="bilinear"`: through Context.export_rgb_resized_batch, h x w may then be larger than
-    a crop on either axis (None: such an item makes the batch raise, as before).  Returns the surfaces."""
+    a crop on either axis (None: such an item makes the batch raise, as before).  `interp="area"`: through Context.export_rgb_reduced_batch, h x w may
+    also be up to 256 times smaller than a crop.  Returns the surfaces."""
     flt = None if interp is None else _filter_of(interp)
     if tensor.dim() != 4:
         raise ValueError("a batch tensor has shape (N, 3, h, w), (N, h, w, 3) or (N, h, w, 4)")
@@ -432,7 +454,9 @@ def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sam
         if s.dtype.itemsize != es:
             raise ValueError("tensor dtype does not fit the surface of item %d: %s" % (k, s.dtype))
         surfaces.append(s)
-    if n and flt is not None:
+    if n and interp == "area":
+        pics[0].ctx.export_rgb_reduced_batch(surfaces, pics, crops, chroma_pos or 0, scale, bias, flt)
+    elif n and flt is not None:
         pics[0].ctx.export_rgb_resized_batch(surfaces, pics, crops, chroma_pos or 0, scale, bias, flt)
     elif n:
         pics[0].ctx.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos or 0, scale, bias)
@@ -612,7 +636,7 @@ class Context:
     def colour_destroy(self, h):
         _chk(self.lib.dav1d_hip_colour_destroy(self.h, h), "colour_destroy")
 
-    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None):
+    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None, _reduced=False):
         """dav1d_hip_surface_export_rgb_scaled_batch: item k gets what pics[k].export_rgb_scaled(surfaces[k], crops[k], chroma_pos, scale, bias) writes,
         all items in one launch (two when raster and twin-only pictures are mixed).  Pictures may repeat; `crops` is None (every item whole) or a
         rectangle (x0, y0, w, h) per item.  One format, one sample type and one pixel size (8 bit, or 10 / 12 bit) per batch.  Asynchronous like
@@ -625,7 +649,10 @@ class Context:
         rects = None if crops is None else (SurfaceRect * max(n, 1))(*[SurfaceRect(*[int(v) for v in r]) for r in crops])
         p = DevicePicture._rgb_params(chroma_pos, scale, bias)
         bad = C.c_int(-1)
-        if _filter is None:
+        if _reduced:
+            rc = self.lib.dav1d_hip_surface_export_rgb_reduced_batch(self.h, n, dst, src, rects, C.byref(p), int(_filter), C.byref(bad))
+            what = "surface_export_rgb_reduced_batch"
+        elif _filter is None:
             rc, what = self.lib.dav1d_hip_surface_export_rgb_scaled_batch(self.h, n, dst, src, rects, C.byref(p), C.byref(bad)), "surface_export_rgb_scaled_batch"
         else:
             rc = self.lib.dav1d_hip_surface_export_rgb_resized_batch(self.h, n, dst, src, rects, C.byref(p), int(_filter), C.byref(bad))
@@ -637,6 +664,11 @@ class Context:
         chroma_pos, scale, bias, filter=filter) writes — a surface may be larger than its crop on either axis, and the items of a batch may mix axes
         that go up, down and nowhere."""
         self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter)
+
+    def export_rgb_reduced_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_reduced_batch: export_rgb_resized_batch whose item k gets what pics[k].export_rgb_reduced(surfaces[k], crops[k],
+        chroma_pos, scale, bias, filter=filter) writes — items over 8:1 (up to 256:1), under it and going up mix freely."""
+        self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter, _reduced=True)
 
     # ---- batched entry points (host task arrays, device arenas)
     def itx_add_batch(self, dst, tasks, coef):

@@ -92,6 +92,9 @@ struct Dav1dHipContext {
     unsigned batch_next = 0;
     std::vector<void *> batch_retired_host, batch_retired_dev;
     std::vector<uint8_t> batch_plan;            // what the checks of a batch found per item, kept for the pass that fills the table (grows to the largest batch)
+    // the reduced pictures Q of dav1d_hip_surface_export_rgb_reduced (surface_reduce.hip): grown on demand (an outgrown one joins batch_retired_dev), freed by dav1d_hip_close
+    uint8_t *reduce_scratch = nullptr;
+    size_t reduce_cap = 0;
 };
 
 // Device memory for the task list of one *_batch call, taken from a pool of the context.  hipMalloc + hipFree per call was the

@@ -176,6 +176,7 @@ void dav1d_hip_close(Dav1dHipContext *c) {
     }
     for (void *q : c->batch_retired_host) hipHostFree(q);
     for (void *q : c->batch_retired_dev) hipFree(q);
+    if (c->reduce_scratch) hipFree(c->reduce_scratch);
     if (c->gather_dev) hipFree(c->gather_dev);
     if (c->segtab_dev) hipFree(c->segtab_dev);
     if (c->pending_slab) hipHostFree(c->pending_slab);

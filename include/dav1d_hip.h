@@ -288,7 +288,7 @@ DAV1D_HIP_API int dav1d_hip_surface_export_grain(Dav1dHipContext *c, const Dav1d
  * host allocation and no host wait (the weights are computed in the kernel).
  * Errors, before anything is enqueued: everything dav1d_hip_surface_export refuses, with its code, except the size rule; -EINVAL for a crop outside the
  * picture, an empty crop, an odd x0 / y0 where the layout subsamples that axis, odd band rows; -ENOTSUP for dst->w > w, dst->h > h, w > 8 dst->w,
- * h > 8 dst->h (upscaling and ratios above 8 are not built).
+ * h > 8 dst->h (this call serves neither upscaling nor ratios above 8; dav1d_hip_surface_export_rgb_resized and _reduced below do, for RGB).
  * dav1d_hip_surface_scaled_rows_needed is host arithmetic: the number of source luma rows, counted from the top of the picture, that must be complete
  * before destination rows [0, drow1) can be exported — the maximum over luma and chroma of y0 + ceil(r1 sh / dh), chroma shifted up by ss_ver, clamped
  * to the picture's height — so that an application can follow dav1d_hip_frame_set_progress_callback band by band; a negative errno for what the export
@@ -409,6 +409,46 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_resized(Dav1dHipContext *c, const
 DAV1D_HIP_API int dav1d_hip_surface_rgb_resized_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                             const Dav1dHipRgbParams *params, int filter, int drow1);
 DAV1D_HIP_API int dav1d_hip_surface_export_rgb_resized_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst /* [n] */,
+                                                             const Dav1dHipPicture *const *src /* [n] */,
+                                                             const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
+                                                             const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */, int filter,
+                                                             int *bad_item /* may be NULL */);
+/* The same exports at thumbnail scale (dav1d_amd/csrc/surface_reduce.hip): an axis may go down by any ratio up to
+ * DAV1D_HIP_SURFACE_REDUCE_MAX : 1.  The calls above keep refusing w > 8 dst->w and h > 8 dst->h; these are entry points of their own.
+ * R' works per plane and per axis, the vertical pass first, on the windows of dav1d_hip_surface_export_scaled, like R above:
+ *   d > s:  R's linear interpolation, unchanged.
+ *   d <= s: S's area rule, unchanged, for every s (no s <= 8 d): the cumulative 12-bit weights, at most ceil(s / d) + 1 <= 257 taps, never negative,
+ *           4096 in sum; a fully covered sample keeps a weight of at least 15 up to 256:1.
+ * The arithmetic after the weights is S's: t = (sum wy P + 8) >> 4 (the sum below 2^24, t below 2^20), out = (sum wx t + (1 << 19)) >> 20 (the sum
+ * below 2^32); no clip is needed.  A constant plane stays constant.
+ * dav1d_hip_surface_export_rgb_reduced writes byte for byte what dav1d_hip_surface_export_rgb(c, dst, Q, params, drow0, drow1) would write, Q being
+ * the picture of dst->w x dst->h samples, of src's layout and bpc, whose planes are R' of the crop windows.  Everything else is
+ * dav1d_hip_surface_export_rgb_resized's: the formats, the samples, chroma_pos 0 / 1 / 2 with cl() against Q's chroma size, normalisation, alpha, the
+ * matrix and range rules, even band rows, dav1d_hip_last_kernel_ms, a const `src` (a DAV1D_HIP_TWIN_ONLY picture stays one), nothing written outside
+ * the visible destination samples of the rows asked for.  Where no plane axis exceeds 8:1 the bytes are those of
+ * dav1d_hip_surface_export_rgb_resized.  `filter` (DAV1D_HIP_RESIZE_BILINEAR) names the rule of the axes that go up.
+ * Unlike there, Q does reach memory where an axis exceeds 8:1: a streaming kernel writes its planes into scratch memory of the context (grown on
+ * demand, kept, freed by dav1d_hip_close; in the steady state no allocation and no host wait), and the export reads them back — at most two reducing
+ * and two exporting launches, all on the context's stream between the events dav1d_hip_last_kernel_ms reads.  The items go to the device through the
+ * staging ring of dav1d_hip_surface_export_rgb_scaled_batch, for the single call as well.
+ * Limitations.  That of dav1d_hip_surface_export_rgb_scaled: every plane is resampled on its own grid, no phase-corrected chroma.  And the weights
+ * stay 12-bit: at hundreds of taps a fully covered sample weighs 15 or 16 of 4096 where the exact figure lies between, so the deviation from an exact
+ * area mean grows with the local contrast of the picture (DESIGN.md 10.8 has the bound and what was measured).  No film grain.
+ * Errors, before anything is enqueued or written: those of dav1d_hip_surface_export_rgb_resized, in its order and with its codes, except that the
+ * ratio rule is w > 256 dst->w or h > 256 dst->h (-ENOTSUP, whatever the other axis does; no chroma axis exceeds 256:1 then either); -ENOTSUP for an
+ * unknown filter and -EXDEV where that call has them; -ENOMEM when the scratch or the staging slot cannot be had.
+ * dav1d_hip_surface_rgb_reduced_rows_needed is dav1d_hip_surface_rgb_resized_rows_needed without the refusal: ceil(r s / d) for every d <= s.  It is a
+ * promise about reads: a band [drow0, drow1) reads no source row at or beyond it.
+ * dav1d_hip_surface_export_rgb_reduced_batch is dav1d_hip_surface_export_rgb_resized_batch with this contract per item — the same uniformity rules,
+ * DAV1D_HIP_SURFACE_BATCH_MAX, *bad_item, n == 0, and the unknown filter as a fault of the call as a whole; items over 8:1, under it and going up
+ * mix freely (those no axis takes past 8:1 are exported straight from their source in the same launch). */
+#define DAV1D_HIP_SURFACE_REDUCE_MAX 256
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_reduced(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                       const Dav1dHipSurfaceRect *crop /* NULL = everything */,
+                                                       const Dav1dHipRgbParams *params /* NULL = all zero */, int filter, int drow0, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_rgb_reduced_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
+                                                            const Dav1dHipRgbParams *params, int filter, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_reduced_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst /* [n] */,
                                                              const Dav1dHipPicture *const *src /* [n] */,
                                                              const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
                                                              const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */, int filter,

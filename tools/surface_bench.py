@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -29,6 +29,11 @@ float16 at chroma_pos 0.  The 32 pictures share one host image (their device mem
 planar float16; (b) lin + matrix, planar float16; (c) lin + matrix + enc, packed RGBA float16 normalised, chroma_pos 1 — each against
 dav1d_hip_surface_export_rgb to the same format and sample with the same parameters, in the same run on the same pictures: the new call moves the
 yardstick's bytes and adds three to six table reads a pixel.  --cells 1,2,4: (a) and (c) again with the context option colour_cells set (the cells a wave takes).
+--reduced: dav1d_hip_surface_export_rgb_reduced, the whole 8K picture to 224 x 224 RGB planar float16 at chroma_pos 1 (34:1 and 19:1), from twin-only
+and from raster sources, against the chain a user can run without it: dav1d_hip_surface_export_scaled at 8:1 to planar native into a pre-allocated
+picture, then dav1d_hip_surface_export_rgb_resized from that to 224 x 224.  The variants alternate within a round, at least ten rounds; per variant the
+device time between two events around the timed calls, the host clock around issuing them and the final sync, and dav1d_hip_last_kernel_ms of the
+last call.  Then dav1d_hip_surface_export_rgb_reduced_batch: 64 crops of 7168 x 4032 of the pictures in rotation to (64, 3, 224, 224).
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -329,6 +334,86 @@ def rgb_scaled_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def reduced_runs(a, ctx, ev, pics, src_bytes):
+    """the one call against export_scaled 8:1 into a picture + export_rgb_resized from it; then a batch of 64"""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    dw = dh = 224
+    mw, mh = w // 8, h // 8
+    rounds, calls = max(a.repeats, 10), min(a.calls, 40)
+    tmps = [ctx.picture(mw, mh, layout, bpc) for _ in range(a.pairs)]
+    views = [api.Surface.wrap(ctx, [t.pic.p[pl].data for pl in range(3)], [t.pic.p[pl].stride for pl in range(3)], mw, mh, layout, bpc,
+                              api.SURFACE_PLANAR, api.SAMPLE_NATIVE) for t in tmps]
+    surfs = [ctx.surface(dw, dh, layout, bpc, api.SURFACE_RGB_PLANAR, api.SAMPLE_F16) for _ in range(a.pairs)]
+    out_bytes, mid = 3 * 2 * dw * dh, 2 * (mw * mh + 2 * ((mw + 1) // 2) * ((mh + 1) // 2))
+    q_bytes = 2 * (dw * dh + 2 * (dw // 2) * (dh // 2))
+
+    def chain(k, state):
+        p = pics[k % a.pairs]
+        p.pic.twin_ok = state
+        p.export_scaled(views[k % a.pairs], None)
+        tmps[k % a.pairs].export_rgb_resized(surfs[k % a.pairs], None, 1)
+
+    def reduced(k, state):
+        p = pics[k % a.pairs]
+        p.pic.twin_ok = state
+        p.export_rgb_reduced(surfs[k % a.pairs], None, 1)
+    runs = []
+    for sname, state in (("twin-only", api.TWIN_ONLY), ("raster", 0)):
+        yard = "export_scaled 8:1 + export_rgb_resized to 224x224, %s source" % sname
+        runs.append((yard, src_bytes + 2 * mid + out_bytes, lambda k, state=state: chain(k, state), None))
+        runs.append(("export_rgb_reduced to 224x224, %s source" % sname, src_bytes + 2 * q_bytes + out_bytes, lambda k, state=state: reduced(k, state), yard))
+    n = 64
+    bsurfs = [ctx.surface(dw, dh, layout, bpc, api.SURFACE_RGB_PLANAR, api.SAMPLE_F16) for _ in range(n)]
+    cw_, ch_ = min(w, 7168) & ~1, min(h, 4032) & ~1
+    crops = [(((w - cw_) * (k % 8) // 7) & ~1, ((h - ch_) * (k // 8) // 7) & ~1, cw_, ch_) for k in range(n)]
+    bytes_batch = n * (2 * (cw_ * ch_ + 2 * (cw_ // 2) * (ch_ // 2)) + 2 * q_bytes + out_bytes)
+    for sname, state in (("twin-only", api.TWIN_ONLY), ("raster", 0)):
+        def batch(k, state=state):
+            for p in pics[:a.pairs]:
+                p.pic.twin_ok = state
+            ctx.export_rgb_reduced_batch(bsurfs, [pics[(k + i) % a.pairs] for i in range(n)], crops, 1)
+        runs.append(("export_rgb_reduced_batch, 64 crops of %dx%d to (64, 3, 224, 224), %s sources" % (cw_, ch_, sname), bytes_batch, batch, None))
+    print("# surface_bench --reduced on %s: %dx%d 4:2:0 %d-bit sources, %d pictures / surfaces in rotation, 3 warm-up + %d timed calls per variant and round (batch: 4), %d rounds, "
+          "the variants alternated within a round" % (socket.gethostname(), w, h, bpc, a.pairs, calls, rounds))
+    print("# bytes per call = bytes read + bytes written, from the shapes (the chain writes and reads the 8:1 planes, the new call Q); device ms between two events around the "
+          "timed calls; host ms: the clock around issuing them and the sync; last ms: dav1d_hip_last_kernel_ms of the last call")
+    results = {r[0]: [] for r in runs}
+    for rnd in range(rounds):
+        for name, nbytes, call, _ in runs:
+            nc = 4 if "batch" in name else calls
+            for k in range(3):
+                call(k)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ev.start()
+            for k in range(nc):
+                call(k)
+            ms = ev.stop_ms() / nc
+            host = (time.perf_counter() - t0) * 1e3 / nc
+            last = ctx.last_kernel_ms()
+            results[name].append((ms, host, last))
+            print("round %2d  %-96s device %8.4f ms/call  host %8.4f  last %8.4f  %7.1f MB/call  %7.0f GB/s  %5.1f %% of copy ceiling"
+                  % (rnd, name, ms, host, last, nbytes / 1e6, nbytes / ms / 1e6, nbytes / ms / 1e6 / (COPY_TBS * 10)))
+    print("# summary (median [min .. max] over the rounds)")
+    for name, nbytes, _, _ in runs:
+        cols = [sorted(v[i] for v in results[name]) for i in range(3)]
+        med = [c[len(c) // 2] for c in cols]
+        print("summary   %-96s device %8.4f [%8.4f .. %8.4f]  host %8.4f [%8.4f .. %8.4f]  last %8.4f [%8.4f .. %8.4f] ms   median %7.0f GB/s, %5.1f %% of the %.1f TB/s copy ceiling"
+              % (name, med[0], cols[0][0], cols[0][-1], med[1], cols[1][0], cols[1][-1], med[2], cols[2][0], cols[2][-1], nbytes / med[0] / 1e6,
+                 nbytes / med[0] / 1e6 / (COPY_TBS * 10), COPY_TBS))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        for i, clock in ((0, "device"), (1, "host")):
+            v, u = sorted(x[i] for x in results[name]), sorted(x[i] for x in results[yard])
+            ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+            print("condition %-64s %-6s median %.4f ms <= chain median %.4f ms + its spread %.4f ms: %s"
+                  % (name, clock, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met"))
+    for s in tmps + surfs + bsurfs + pics:
+        s.free()
+    ctx.close()
+
+
 def colour_runs(a, ctx, ev, pics, src_bytes):
     """the colour-managed export against export_rgb to the same format and sample"""
     w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
@@ -487,6 +572,7 @@ def main():
     ap.add_argument("--rgb-scaled", action="store_true", help="dav1d_hip_surface_export_rgb_scaled against export_scaled into a picture + export_rgb from it")
     ap.add_argument("--batch", action="store_true", help="dav1d_hip_surface_export_rgb_scaled_batch against the N single calls it replaces")
     ap.add_argument("--colour", action="store_true", help="dav1d_hip_surface_export_rgb_colour (PQ / BT.2020 -> sRGB / BT.709) against export_rgb to the same format")
+    ap.add_argument("--reduced", action="store_true", help="dav1d_hip_surface_export_rgb_reduced to 224 x 224 against export_scaled 8:1 + export_rgb_resized; a batch of 64")
     ap.add_argument("--cells", type=lambda v: [int(x) for x in v.split(",") if x], default=[], help="--colour: variants (a) and (c) again with these values of the option colour_cells")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
@@ -531,6 +617,8 @@ def main():
         return batch_runs(a, ctx, ev, pics)
     if a.colour:
         return colour_runs(a, ctx, ev, pics, src_bytes)
+    if a.reduced:
+        return reduced_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
