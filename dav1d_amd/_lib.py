@@ -108,6 +108,7 @@ SYMBOLS = [
     "dav1d_hip_surface_export_rgb_scaled", "dav1d_hip_surface_rgb_scaled_rows_needed", "dav1d_hip_surface_export_rgb_scaled_batch",    "dav1d_hip_colour_create", "dav1d_hip_colour_destroy", "dav1d_hip_surface_export_rgb_colour", "dav1d_hip_colour_tables",
     "dav1d_hip_surface_export_rgb_resized", "dav1d_hip_surface_rgb_resized_rows_needed", "dav1d_hip_surface_export_rgb_resized_batch",
     "dav1d_hip_surface_export_rgb_reduced", "dav1d_hip_surface_rgb_reduced_rows_needed", "dav1d_hip_surface_export_rgb_reduced_batch",
+    "dav1d_hip_surface_export_rgb_colour_reduced", "dav1d_hip_surface_export_rgb_colour_reduced_batch",
 ]
 
 
@@ -325,6 +326,8 @@ def load(path=None):
         "dav1d_hip_surface_export_rgb_reduced": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i, i]),
         "dav1d_hip_surface_export_rgb_reduced_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), i, P(i)]),
         "dav1d_hip_surface_rgb_reduced_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
+        "dav1d_hip_surface_export_rgb_colour_reduced": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), vp, i, i, i]),
+        "dav1d_hip_surface_export_rgb_colour_reduced_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), vp, i, P(i)]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

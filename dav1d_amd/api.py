@@ -231,6 +231,15 @@ class DevicePicture:
         _chk(min(n, 0), "surface_rgb_reduced_rows_needed")
         return n
 
+    def export_rgb_colour_reduced(self, surface, colour, crop=None, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_colour_reduced: export_rgb_reduced followed by the tables of `colour` (Context.colour / Context.colour_for) as in
+        export_rgb_colour — the rectangle `crop` at the surface's size, any ratio up to 256:1 down and any size up, linearised, gamut-mapped and
+        re-encoded.  Float surfaces only (F32, F16); the colour stage runs on the resampled code values.  rgb_reduced_rows_needed serves this call as
+        it is.  Asynchronous like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_colour_reduced(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), colour,
+                                                                      int(filter), row0, row1), "surface_export_rgb_colour_reduced")
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -463,6 +472,83 @@ def export_batch_to_tensor(pics, tensor, crops=None, matrix=1, full_range=0, sam
     return surfaces
 
 
+def _colour_sample(tensor):
+    import torch
+    if tensor.dtype not in (torch.float32, torch.float16):
+        raise ValueError("the colour-managed export writes float32 or float16 tensors")
+    return SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_F16
+
+
+def export_colour_to_tensor(pic, tensor, colour, crop=None, matrix=1, full_range=0, chroma_pos=None, scale=None, bias=None):
+    """Fills a float32 / float16 torch tensor with the rectangle `crop` = (x0, y0, w, h) of the picture (None: all of it) at the TENSOR's size, through
+    the tables of `colour` (Context.colour / Context.colour_for): DevicePicture.export_rgb_colour_reduced.  Shape (3, h, w) gets R, G, B planes,
+    (h, w, 3) / (h, w, 4) packed RGB / RGBA; h x w may be up to 256 times smaller than the crop on either axis, or larger.  Shape and stride rules are
+    export_to_tensor's: a device tensor, unit stride along a row, the channels of a packed tensor next to each other, and a shape that reads both
+    ways, (3, n, 3) or (3, n, 4), raises ValueError.  Returns the surface."""
+    if colour is None:
+        raise ValueError("export_colour_to_tensor needs a colour handle")
+    if tensor.dim() != 3:
+        raise ValueError("an RGB tensor has shape (3, h, w), (h, w, 3) or (h, w, 4)")
+    shape = tuple(int(v) for v in tensor.shape)
+    chw, hwc = shape[0] == 3, shape[2] in (3, 4)
+    if chw and hwc:
+        raise ValueError("a tensor of shape %s can be read as (3, h, w) and as (h, w, 3 or 4): not accepted" % (shape,))
+    if not chw and not hwc:
+        raise ValueError("an RGB tensor has shape (3, h, w), (h, w, 3) or (h, w, 4)")
+    if not tensor.is_cuda or tensor.stride(-1) != 1:
+        raise ValueError("export_colour_to_tensor needs a device tensor with unit stride along a row")
+    es = tensor.element_size()
+    if hwc:
+        if tensor.stride(1) != shape[2]:
+            raise ValueError("a packed RGB tensor has its channels next to each other")
+        h, w = shape[0], shape[1]
+        fmt, ptrs, strides = (SURFACE_RGB_PACKED if shape[2] == 3 else SURFACE_RGBA_PACKED), [tensor.data_ptr()], [tensor.stride(0) * es]
+    else:
+        h, w = shape[1], shape[2]
+        fmt, ptrs, strides = SURFACE_RGB_PLANAR, [tensor[k].data_ptr() for k in range(3)], [tensor.stride(1) * es] * 3
+    s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, _colour_sample(tensor), matrix, full_range)
+    pic.export_rgb_colour_reduced(s, colour, crop, chroma_pos or 0, scale, bias)
+    return s
+
+
+def export_colour_batch_to_tensor(pics, tensor, colour, crops=None, matrix=1, full_range=0, chroma_pos=None, scale=None, bias=None):
+    """Fills one float32 / float16 torch tensor with N pictures (or N regions: pictures may repeat) through Context.export_rgb_colour_reduced_batch:
+    `tensor` of shape (N, 3, h, w) gets R, G, B planes, (N, h, w, 3) / (N, h, w, 4) packed RGB / RGBA; crops[k] = (x0, y0, w, h) (`crops` None: the
+    whole picture) is the rectangle of pics[k] that goes to h x w, at any ratio up to 256:1 down and any size up, through the tables of `colour`.
+    Shape and stride rules are export_batch_to_tensor's.  Returns the surfaces."""
+    if colour is None:
+        raise ValueError("export_colour_batch_to_tensor needs a colour handle")
+    if tensor.dim() != 4:
+        raise ValueError("a batch tensor has shape (N, 3, h, w), (N, h, w, 3) or (N, h, w, 4)")
+    shape = tuple(int(v) for v in tensor.shape)
+    n = shape[0]
+    if len(pics) != n or (crops is not None and len(crops) != n):
+        raise ValueError("a tensor of shape %s takes %d pictures, and %d crops if any" % (shape, n, n))
+    chw, hwc = shape[1] == 3, shape[3] in (3, 4)
+    if chw and hwc:
+        raise ValueError("a tensor of shape %s can be read as (N, 3, h, w) and as (N, h, w, 3 or 4): not accepted" % (shape,))
+    if not chw and not hwc:
+        raise ValueError("a batch tensor has shape (N, 3, h, w), (N, h, w, 3) or (N, h, w, 4)")
+    if not tensor.is_cuda:
+        raise ValueError("export_colour_batch_to_tensor needs a device tensor")
+    if tensor.stride(-1) != 1:
+        raise ValueError("export_colour_batch_to_tensor needs unit stride along a row")
+    if hwc and tensor.stride(2) != shape[3]:
+        raise ValueError("a packed RGB tensor has its channels next to each other")
+    sample = _colour_sample(tensor)
+    es = tensor.element_size()
+    h, w = (shape[1], shape[2]) if hwc else (shape[2], shape[3])
+    fmt = SURFACE_RGB_PLANAR if chw else SURFACE_RGB_PACKED if shape[3] == 3 else SURFACE_RGBA_PACKED
+    surfaces = []
+    for k, pic in enumerate(pics):
+        t = tensor[k]
+        ptrs, strides = ([t.data_ptr()], [t.stride(0) * es]) if hwc else ([t[c].data_ptr() for c in range(3)], [t.stride(1) * es] * 3)
+        surfaces.append(Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range))
+    if n:
+        pics[0].ctx.export_rgb_colour_reduced_batch(surfaces, pics, colour, crops, chroma_pos or 0, scale, bias)
+    return surfaces
+
+
 class _List:
     def __init__(self, ctx, kind, tasks, dtype):
         self.ctx, self.kind = ctx, kind
@@ -636,7 +722,7 @@ class Context:
     def colour_destroy(self, h):
         _chk(self.lib.dav1d_hip_colour_destroy(self.h, h), "colour_destroy")
 
-    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None, _reduced=False):
+    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None, _reduced=False, _colour=None):
         """dav1d_hip_surface_export_rgb_scaled_batch: item k gets what pics[k].export_rgb_scaled(surfaces[k], crops[k], chroma_pos, scale, bias) writes,
         all items in one launch (two when raster and twin-only pictures are mixed).  Pictures may repeat; `crops` is None (every item whole) or a
         rectangle (x0, y0, w, h) per item.  One format, one sample type and one pixel size (8 bit, or 10 / 12 bit) per batch.  Asynchronous like
@@ -649,7 +735,10 @@ class Context:
         rects = None if crops is None else (SurfaceRect * max(n, 1))(*[SurfaceRect(*[int(v) for v in r]) for r in crops])
         p = DevicePicture._rgb_params(chroma_pos, scale, bias)
         bad = C.c_int(-1)
-        if _reduced:
+        if _colour is not None:
+            rc = self.lib.dav1d_hip_surface_export_rgb_colour_reduced_batch(self.h, n, dst, src, rects, C.byref(p), _colour, int(_filter), C.byref(bad))
+            what = "surface_export_rgb_colour_reduced_batch"
+        elif _reduced:
             rc = self.lib.dav1d_hip_surface_export_rgb_reduced_batch(self.h, n, dst, src, rects, C.byref(p), int(_filter), C.byref(bad))
             what = "surface_export_rgb_reduced_batch"
         elif _filter is None:
@@ -669,6 +758,14 @@ class Context:
         """dav1d_hip_surface_export_rgb_reduced_batch: export_rgb_resized_batch whose item k gets what pics[k].export_rgb_reduced(surfaces[k], crops[k],
         chroma_pos, scale, bias, filter=filter) writes — items over 8:1 (up to 256:1), under it and going up mix freely."""
         self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter, _reduced=True)
+
+    def export_rgb_colour_reduced_batch(self, surfaces, pics, colour, crops=None, chroma_pos=0, scale=None, bias=None, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_colour_reduced_batch: export_rgb_reduced_batch whose item k gets what
+        pics[k].export_rgb_colour_reduced(surfaces[k], colour, crops[k], chroma_pos, scale, bias, filter=filter) writes.  One handle serves all items:
+        float surfaces only, and every picture has the handle's bit depth."""
+        if colour is None:
+            raise ValueError("export_rgb_colour_reduced_batch needs a colour handle")
+        self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter, _colour=colour)
 
     # ---- batched entry points (host task arrays, device arenas)
     def itx_add_batch(self, dst, tasks, coef):

@@ -41,7 +41,7 @@ struct Dav1dHipContext {
     int chunk_upload;           // 0: a frame's chunks go up as one transfer at frame end; 1: each chunk as it is submitted (DAV1D_HIP_CHUNK_UPLOAD)
     int recon_coop_below;       // paired kernels: launches of fewer groups than this take the cooperative form (recon.hip; DAV1D_HIP_RECON_COOP_BELOW)
     int post_bands;             // bands of the pipelined post filters, 0 = stage by stage (DAV1D_HIP_POST_BANDS)
-    int colour_cells;           // cells a wave of the colour-managed export takes, 0 (default) = cells_per_wave of surface_colour.hip (DAV1D_HIP_COLOUR_CELLS; a measuring and testing knob)
+    int colour_cells;           // cells a wave of the colour-managed export takes, 0 (default) = cells_per_wave of surface_colour.h, for surface_colour.hip and surface_colour_reduce.hip (DAV1D_HIP_COLOUR_CELLS; a measuring and testing knob)
     int recon_pair_streams;     // side streams the paired launches of a recon list are dealt over (DAV1D_HIP_RECON_PAIR_STREAMS, 1 .. 3; default 2)
     int recon_pair_first;       // ... starting at side stream 1 .. 3 (DAV1D_HIP_RECON_PAIR_FIRST; default 2): which HARDWARE queue a stream shares with which other is a matter of the order the
                                 // streams were made in (the runtime deals them over GPU_MAX_HW_QUEUES = 4 queues), profiles/r06/hw_queues.txt
@@ -92,7 +92,7 @@ struct Dav1dHipContext {
     unsigned batch_next = 0;
     std::vector<void *> batch_retired_host, batch_retired_dev;
     std::vector<uint8_t> batch_plan;            // what the checks of a batch found per item, kept for the pass that fills the table (grows to the largest batch)
-    // the reduced pictures Q of dav1d_hip_surface_export_rgb_reduced (surface_reduce.hip): grown on demand (an outgrown one joins batch_retired_dev), freed by dav1d_hip_close
+    // the reduced pictures Q of dav1d_hip_surface_export_rgb_reduced (surface_reduce.hip) and dav1d_hip_surface_export_rgb_colour_reduced (surface_colour_reduce.hip): grown on demand (an outgrown one joins batch_retired_dev), freed by dav1d_hip_close
     uint8_t *reduce_scratch = nullptr;
     size_t reduce_cap = 0;
 };

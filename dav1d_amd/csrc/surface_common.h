@@ -1,6 +1,7 @@
 // What the output units share (surface.hip: the plain export; surface_grain.hip: the export with film grain fused in; surface_scale.hip: the export
 // with a crop and a scaler in front; surface_rgb.hip: tensor-ready RGB; surface_rgb_scale.hip: that behind the scaler; surface_batch.hip: many of those in one launch;
-// surface_resize.hip: both with axes that may go up): the 8-sample unit and
+// surface_resize.hip: both with axes that may go up; surface_reduce.hip: both at thumbnail scale; surface_colour.hip and surface_colour_reduce.hip:
+// tensor-ready RGB through a colour stage, at the picture's size and at any size): the 8-sample unit and
 // its loads and stores, the output sample functors, the kernel arguments and how a call is checked and turned into them.  See surface.hip for the
 // layout of a wave (8 rows x 8 units, a 64 x 8 cell of a plane).
 #pragma once
@@ -388,7 +389,7 @@ __device__ __forceinline__ void taps_down(const int pos, const uint32_t up, cons
 
 // One wave's share of a tensor-ready export: cell g (counted across, then down) of the call described by ax, all 64 lanes of the wave call.  `fn`
 // turns the three clipped integers of a pixel into its three output samples (together: a colour matrix needs all of them) and has the opaque
-// alpha.  The kernels of surface_rgb.hip (a cell a workgroup) and surface_colour.hip (a wave of a workgroup takes several cells in a loop: a
+// alpha.  The kernels of surface_rgb.hip (a cell a workgroup), surface_colour.hip and surface_colour_reduce.hip (a wave of a workgroup takes several cells in a loop: a
 // lane without work returns from here, which is the `continue` of that loop) are this function.
 template <typename pixel, bool TILED, int SSH, int SSV, typename Fn>
 __device__ __forceinline__ void rgbx_cell(const RgbxArgs &ax, const int g, const Fn &fn)

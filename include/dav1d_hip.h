@@ -505,6 +505,42 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const 
 DAV1D_HIP_API int dav1d_hip_colour_tables(int bpc, int trc_in, int pri_in, int trc_out, int pri_out, float white_nits, float peak_nits,
                                           float *lin /* [1 << bpc] */, float m[9], int *has_matrix,
                                           uint16_t *enc /* [DAV1D_HIP_COLOUR_ENC_N] */, int *has_enc);
+/* The colour-managed export at ANY size (dav1d_amd/csrc/surface_colour_reduce.hip): crop, resize, reduce and batch with the colour
+ * stage behind them.  dav1d_hip_surface_export_rgb_colour keeps refusing a surface of another size; these are entry points of their own.
+ * Nothing numerical is new.  Let Q be the picture of dst->w x dst->h samples, of src's layout and bpc, whose planes are R' of the crop windows: exactly
+ * the Q of dav1d_hip_surface_export_rgb_reduced — the area rule S for every d <= s up to DAV1D_HIP_SURFACE_REDUCE_MAX : 1, R's linear interpolation
+ * for d > s.  dav1d_hip_surface_export_rgb_colour_reduced writes byte for byte what dav1d_hip_surface_export_rgb_colour(c, dst, Q, params, colour,
+ * drow0, drow1) would write: formats RGB_PLANAR, RGB_PACKED, RGBA_PACKED; samples F32 and F16 only; chroma_pos 0 / 1 / 2 with cl() against Q's chroma
+ * size; steps 1 to 4 of the definition above, every float operation rounded on its own and nothing fused; the normalisation, alpha 1.0, the matrix,
+ * range, I400 and matrix-0 rules; even band rows as in dav1d_hip_surface_export_rgb_reduced.  `filter` is DAV1D_HIP_RESIZE_BILINEAR.
+ * The colour stage runs on Q's code values: the pictures are resampled in their own transfer and linearised afterwards.  Scaling in linear light is NOT
+ * built (a limitation: an area mean of PQ or gamma codes is darker at high-contrast edges than the mean of the light they stand for); the limitations of
+ * dav1d_hip_surface_export_rgb_reduced hold as well.  No film grain.
+ * dav1d_hip_surface_rgb_reduced_rows_needed serves this call unchanged: a band [drow0, drow1) reads no source row at or beyond it.
+ * Q reaches memory for every item here, whatever its ratio (the tables of the colour stage and the scaler's window do not fit in LDS together): the
+ * streaming kernel of dav1d_hip_surface_export_rgb_reduced writes it into the same scratch memory of the context (grown on demand, kept, freed by
+ * dav1d_hip_close), the items go through the same staging ring; in the steady state there is no allocation and no host wait.  Everything is
+ * asynchronous on the context's stream, between the events dav1d_hip_last_kernel_ms reads; `src` is const and a DAV1D_HIP_TWIN_ONLY picture stays
+ * one; nothing is written outside the visible destination samples of the rows asked for.  Launches per call are bounded whatever n is: at most two
+ * that make Q (raster and twin-only sources) and one that exports per chroma subsampling present among the items (4:2:0; 4:2:2; 4:4:4 and 4:0:0) —
+ * one for the single call and for a batch of one layout, three at the most.
+ * Errors of the single call, before anything is enqueued or written, in this order: what dav1d_hip_surface_export_rgb_reduced refuses up to and
+ * including the unknown filter, with its codes; -EINVAL for a NULL colour, then for an integer sample (NATIVE, MSB16), then for a handle whose bpc is
+ * not the picture's; -EXDEV for a picture of another device, then for a handle of another device; -ENOMEM as there.
+ * dav1d_hip_surface_export_rgb_colour_reduced_batch writes, for every item i < n, the bytes that the single call writes over the whole of dst[i], and no
+ * other byte; one `params` and one `colour` serve all items.  c, n and filter are checked as in dav1d_hip_surface_export_rgb_reduced_batch; a NULL
+ * colour is a fault of the call as a whole (-EINVAL, *bad_item = -1), found after the filter and before n == 0 returns 0; then NULL dst / src / src[i]
+ * as there; then, in item order, what the single call refuses for the item and -EINVAL for an item whose format or sample differs from item 0's.  An
+ * item whose bpc is not the handle's is refused by the single call's rule, which is stricter than "one pixel size per batch". */
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour_reduced(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                              const Dav1dHipSurfaceRect *crop /* NULL = everything */,
+                                                              const Dav1dHipRgbParams *params /* NULL = all zero */, const Dav1dHipColour *colour,
+                                                              int filter, int drow0, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour_reduced_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst /* [n] */,
+                                                                    const Dav1dHipPicture *const *src /* [n] */,
+                                                                    const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
+                                                                    const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */,
+                                                                    const Dav1dHipColour *colour, int filter, int *bad_item /* may be NULL */);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced | --colour-reduced] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -34,6 +34,12 @@ and from raster sources, against the chain a user can run without it: dav1d_hip_
 picture, then dav1d_hip_surface_export_rgb_resized from that to 224 x 224.  The variants alternate within a round, at least ten rounds; per variant the
 device time between two events around the timed calls, the host clock around issuing them and the final sync, and dav1d_hip_last_kernel_ms of the
 last call.  Then dav1d_hip_surface_export_rgb_reduced_batch: 64 crops of 7168 x 4032 of the pictures in rotation to (64, 3, 224, 224).
+--colour-reduced: dav1d_hip_surface_export_rgb_colour_reduced with the tables of PQ / BT.2020 -> sRGB / BT.709 from twin-only sources, by the method of
+--reduced (variants alternated within a round, at least ten rounds).  1. the whole 8K picture to 224 x 224 planar float16 at chroma_pos 1 against
+dav1d_hip_surface_export_rgb_reduced to the same format; 2. dav1d_hip_surface_export_rgb_colour_reduced_batch, 64 crops of 7168 x 4032 to
+(64, 3, 224, 224), against dav1d_hip_surface_export_rgb_reduced_batch; 3. 8K to 3840 x 2160 RGBA float16 against the only other route to those bytes,
+dav1d_hip_surface_export_scaled into a pre-allocated picture + dav1d_hip_surface_export_rgb_colour from it, with dav1d_hip_surface_export_rgb_scaled
+(no colour stage) next to it for what the trip of Q through memory costs.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -563,6 +569,90 @@ def batch_runs(a, ctx, ev, pics):
     ctx.close()
 
 
+def colour_reduced_runs(a, ctx, ev, pics, src_bytes):
+    """dav1d_hip_surface_export_rgb_colour_reduced and its batch against export_rgb_reduced (no colour stage) to the same format, and at 2:1 against the
+    only other route to those bytes: export_scaled into a picture + export_rgb_colour from it"""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    dw = dh = 224
+    hw, hh = w // 2, h // 2
+    rounds, calls = 1 if a.short else max(a.repeats, 10), min(a.calls, 40)
+    lin, m, enc, has_matrix, has_enc = api.colour_tables(ctx.lib, bpc, 16, 9, 13, 1, 203.0, 1000.0)
+    assert has_matrix and has_enc
+    colour = ctx.colour(lin, m, enc, bpc=bpc)
+    P, K4, F16 = api.SURFACE_RGB_PLANAR, api.SURFACE_RGBA_PACKED, api.SAMPLE_F16
+    surfs = [ctx.surface(dw, dh, layout, bpc, P, F16, matrix=9) for _ in range(a.pairs)]
+    out_bytes, q_bytes = 3 * 2 * dw * dh, 2 * (dw * dh + 2 * (dw // 2) * (dh // 2))
+    for p in pics:
+        p.pic.twin_ok = api.TWIN_ONLY
+    runs = []
+    yard = "export_rgb_reduced to 224x224 planar float16 (yardstick)"
+    runs.append((yard, src_bytes + 2 * q_bytes + out_bytes, lambda k: pics[k % a.pairs].export_rgb_reduced(surfs[k % a.pairs], None, 1), None))
+    runs.append(("1. export_rgb_colour_reduced to 224x224 planar float16", src_bytes + 2 * q_bytes + out_bytes,
+                 lambda k: pics[k % a.pairs].export_rgb_colour_reduced(surfs[k % a.pairs], colour, None, 1), yard))
+    n = 64
+    bsurfs = [ctx.surface(dw, dh, layout, bpc, P, F16, matrix=9) for _ in range(n)]
+    cw_, ch_ = min(w, 7168) & ~1, min(h, 4032) & ~1
+    crops = [(((w - cw_) * (k % 8) // 7) & ~1, ((h - ch_) * (k // 8) // 7) & ~1, cw_, ch_) for k in range(n)]
+    bytes_batch = n * (2 * (cw_ * ch_ + 2 * (cw_ // 2) * (ch_ // 2)) + 2 * q_bytes + out_bytes)
+    yard = "export_rgb_reduced_batch, 64 crops of %dx%d to (64, 3, 224, 224) (yardstick)" % (cw_, ch_)
+    runs.append((yard, bytes_batch, lambda k: ctx.export_rgb_reduced_batch(bsurfs, [pics[(k + i) % a.pairs] for i in range(n)], crops, 1), None))
+    runs.append(("2. export_rgb_colour_reduced_batch, 64 crops of %dx%d to (64, 3, 224, 224)" % (cw_, ch_), bytes_batch,
+                 lambda k: ctx.export_rgb_colour_reduced_batch(bsurfs, [pics[(k + i) % a.pairs] for i in range(n)], colour, crops, 1), yard))
+    tmps = [ctx.picture(hw, hh, layout, bpc) for _ in range(a.pairs)]
+    views = [api.Surface.wrap(ctx, [t.pic.p[pl].data for pl in range(3)], [t.pic.p[pl].stride for pl in range(3)], hw, hh, layout, bpc,
+                              api.SURFACE_PLANAR, api.SAMPLE_NATIVE) for t in tmps]
+    halves = [ctx.surface(hw, hh, layout, bpc, K4, F16, matrix=9) for _ in range(a.pairs)]
+    mid, out4 = 2 * (hw * hh + 2 * ((hw + 1) // 2) * ((hh + 1) // 2)), 4 * 2 * hw * hh
+
+    def chain(k):
+        pics[k % a.pairs].export_scaled(views[k % a.pairs], None)
+        tmps[k % a.pairs].export_rgb_colour(halves[k % a.pairs], colour, 1)
+    yard = "export_scaled 2:1 + export_rgb_colour to %dx%d RGBA float16 (yardstick)" % (hw, hh)
+    runs.append((yard, src_bytes + 2 * mid + out4, chain, None))
+    runs.append(("3. export_rgb_colour_reduced to %dx%d RGBA float16" % (hw, hh), src_bytes + 2 * mid + out4,
+                 lambda k: pics[k % a.pairs].export_rgb_colour_reduced(halves[k % a.pairs], colour, None, 1), yard))
+    runs.append(("   export_rgb_scaled to %dx%d RGBA float16 (no colour stage, no bar: Q never reaches memory)" % (hw, hh), src_bytes + out4,
+                 lambda k: pics[k % a.pairs].export_rgb_scaled(halves[k % a.pairs], None, 1), None))
+    print("# surface_bench --colour-reduced on %s: %dx%d 4:2:0 %d-bit twin-only sources, PQ / BT.2020 to sRGB / BT.709 (lin + matrix + enc), %d pictures / surfaces in rotation, "
+          "3 warm-up + %d timed calls per variant and round (batch: 4), %d rounds, the variants alternated within a round" % (socket.gethostname(), w, h, bpc, a.pairs, calls, rounds))
+    print("# bytes per call = bytes read + bytes written, from the shapes (Q and the chain's planes written and read once); device ms between two events around the timed calls; "
+          "host ms: the clock around issuing them and the sync; last ms: dav1d_hip_last_kernel_ms of the last call")
+    results = {r[0]: [] for r in runs}
+    for rnd in range(rounds):
+        for name, nbytes, call, _ in runs:
+            nc = 4 if "batch" in name else calls
+            for k in range(3):
+                call(k)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ev.start()
+            for k in range(nc):
+                call(k)
+            ms = ev.stop_ms() / nc
+            host = (time.perf_counter() - t0) * 1e3 / nc
+            last = ctx.last_kernel_ms()
+            results[name].append((ms, host, last))
+            print("round %2d  %-100s device %8.4f ms/call  host %8.4f  last %8.4f  %7.1f MB/call  %7.0f GB/s" % (rnd, name, ms, host, last, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (median [min .. max] over the rounds)")
+    for name, nbytes, _, _ in runs:
+        cols = [sorted(v[i] for v in results[name]) for i in range(3)]
+        med = [c[len(c) // 2] for c in cols]
+        print("summary   %-100s device %8.4f [%8.4f .. %8.4f]  host %8.4f [%8.4f .. %8.4f]  last %8.4f [%8.4f .. %8.4f] ms   median %7.0f GB/s"
+              % (name, med[0], cols[0][0], cols[0][-1], med[1], cols[1][0], cols[1][-1], med[2], cols[2][0], cols[2][-1], nbytes / med[0] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(x[0] for x in results[name]), sorted(x[0] for x in results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-84s device median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms: %s (x %.2f)"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met", u[len(u) // 2] / v[len(v) // 2]))
+    ctx.sync()
+    ctx.colour_destroy(colour)
+    for s in tmps + surfs + bsurfs + halves + pics:
+        s.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
@@ -573,6 +663,7 @@ def main():
     ap.add_argument("--batch", action="store_true", help="dav1d_hip_surface_export_rgb_scaled_batch against the N single calls it replaces")
     ap.add_argument("--colour", action="store_true", help="dav1d_hip_surface_export_rgb_colour (PQ / BT.2020 -> sRGB / BT.709) against export_rgb to the same format")
     ap.add_argument("--reduced", action="store_true", help="dav1d_hip_surface_export_rgb_reduced to 224 x 224 against export_scaled 8:1 + export_rgb_resized; a batch of 64")
+    ap.add_argument("--colour-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_colour_reduced and its batch against export_rgb_reduced; at 2:1 against export_scaled + export_rgb_colour")
     ap.add_argument("--cells", type=lambda v: [int(x) for x in v.split(",") if x], default=[], help="--colour: variants (a) and (c) again with these values of the option colour_cells")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
@@ -619,6 +710,8 @@ def main():
         return colour_runs(a, ctx, ev, pics, src_bytes)
     if a.reduced:
         return reduced_runs(a, ctx, ev, pics, src_bytes)
+    if a.colour_reduced:
+        return colour_reduced_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
