@@ -32,6 +32,20 @@ __device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int c) {
     return __builtin_amdgcn_sdot2(__builtin_bit_cast(s2, a), __builtin_bit_cast(s2, b), c, false);
 #endif
 }
+// The first link of a chain of dot2(): c is a value that stays live after it (a rounding offset).  v_dot2c_i32_i16 accumulates in place, so
+// the compiler copies c into the accumulator first — one move per sum; the three-operand form (v_dot2_i32_i16) reads c where it lies.
+// B_SCALAR: b is wave-uniform and travels in an SGPR (the taps of a wave that works on ONE tile).
+template <bool B_SCALAR>
+__device__ __forceinline__ int dot2_seed(uint32_t a, uint32_t b, int c) {
+#ifdef DAV1D_HIP_EMU
+    return __builtin_amdgcn_sdot2(a, b, c, false);
+#else
+    int r;
+    if constexpr (B_SCALAR) asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    else asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+#endif
+}
 // single-instruction forms the compiler does not find on its own for runtime bounds
 __device__ __forceinline__ int med3(int v, int lo, int hi) {           // clamp(v, lo, hi) for lo <= hi
 #ifdef DAV1D_HIP_EMU

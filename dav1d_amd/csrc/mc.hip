@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void mc_twin_kernel(const DevPlanes dst, const 
     __shared__ uint4 smem[(mc_lds_bytes<TW, TH, true>() + 15) / 16];
     const int t0 = (int) dv::xcd_chunk_id(blockIdx.x, gridDim.x) * G;
     if (t0 >= n) return;
-    mc_body<TW, TH, pixel, false, true, true>(dst, refs, n_refs, tiles, t0, dv::imin(G, n - t0), prep, bitdepth_max, smem, nullptr, 0, 0, 0, 0, twin);
+    mc_body<TW, TH, pixel, false, true, true>(dst, refs, n_refs, tiles, t0, dv::imin(G, n - t0), prep, bitdepth_max, smem, nullptr, 0, 0, 0, 0, true, twin);
 }
 
 // every tile shape in one launch: the tiles are ordered by where they read (all shapes interleaved, see

@@ -133,17 +133,52 @@ __device__ __forceinline__ void mc_gather(const McRef rf, const McPred &pd, cons
         const int c_first = rf.src_x - 3 + (rf.hspan & 15), c_last = rf.src_x - 3 + TW - 2 + (rf.hspan >> 4);
         const int y0 = rf.src_y - 3;
         const bool interior = c_first >= 0 && c_last < rw && y0 + row_lo >= 0 && y0 + row_hi <= rh;
+        // Lanes in a grid of rows x pieces, both powers of two (no division): lane -> (row lr of its row group, piece
+        // column lp), the loops step over row groups and piece columns.  Consecutive lanes walk down the rows of one
+        // tile column: 8 of them share a 128-byte line.  Tiles of 4 rows only ever meet the 4-tap / bilinear / unit
+        // sets vertically (blocks of height <= 4, reference GET_V_FILTER): rows 2 .. TH + 4 of the window.
+        constexpr int R0 = TH == 4 ? 2 : 0, NR = TH == 4 ? TH + 3 : WR - 1;
+        constexpr int RG = NR <= 8 ? 8 : NR <= 16 ? 16 : 32;                 // lanes of a row group
+        constexpr int RPAR = mc_cmin(LPT, RG), NRI = (NR + RPAR - 1) / RPAR;
+        constexpr int PG = LPT >= RG ? LPT / RG : 1, NPI = (NCH + PG - 1) / PG;
+        typedef typename std::conditional<HBD, uint4, uint2>::type piece_t;
+        const int lr = l & (RPAR - 1), lp = PG > 1 ? l / RG : 0;
+#ifndef DV_GATHER_PER_PIECE
+        constexpr bool ONE_ROW = NRI == 1 && NCH % PG == 0;                  // one window row per lane, every piece column inside the window
+#else
+        constexpr bool ONE_ROW = false;
+#endif
+        (void) lr; (void) lp; (void) ONE_ROW; (void) NPI;
         if (interior) {
-            // Lanes in a grid of rows x pieces, both powers of two (no division): lane -> (row lr of its row group, piece
-            // column lp), the loops step over row groups and piece columns.  Consecutive lanes walk down the rows of one
-            // tile column: 8 of them share a 128-byte line.  Tiles of 4 rows only ever meet the 4-tap / bilinear / unit
-            // sets vertically (blocks of height <= 4, reference GET_V_FILTER): rows 2 .. TH + 4 of the window.
-            constexpr int R0 = TH == 4 ? 2 : 0, NR = TH == 4 ? TH + 3 : WR - 1;
-            constexpr int RG = NR <= 8 ? 8 : NR <= 16 ? 16 : 32;                 // lanes of a row group
-            constexpr int RPAR = mc_cmin(LPT, RG), NRI = (NR + RPAR - 1) / RPAR;
-            constexpr int PG = LPT >= RG ? LPT / RG : 1, NPI = (NCH + PG - 1) / PG;
-            typedef typename std::conditional<HBD, uint4, uint2>::type piece_t;
-            const int lr = l & (RPAR - 1), lp = PG > 1 ? l / RG : 0;
+            if constexpr (ONE_ROW) {
+                // One row per lane (tiles of 8 rows and more): the row's validity is the only mask — ONE control-flow region around the lane's
+                // loads and stores instead of two per piece.  The pieces the horizontal taps reach are p_lo .. p_hi of the row; a piece
+                // outside is fetched at the nearest one inside (an address this lane loads anyway: no further line moves) and stored where
+                // it belongs: like the stale data it replaces there it only ever meets zero taps.
+                const int wr = R0 + lr, y = y0 + wr;
+                if (lr < NR && wr >= row_lo && wr < row_hi) {
+                    const pixel *prow = src + (dv::mul_i24(y & ~7, rs) + ((y & 7) << 3) + (xa << 3));
+                    const int p_lo = (c_first - xa) >> 3, p_hi = (c_last - xa) >> 3;
+                    piece_t ld[NPI];
+#pragma unroll
+                    for (int pi = 0; pi < NPI; pi++) {
+                        const int pc = dv::clamp3(lp + pi * PG, p_lo, p_hi);
+#ifdef DV_KO_GATHER
+                        ld[pi].x = (unsigned) (size_t) prow; ld[pi].y = (unsigned) pc; if constexpr (HBD) { ld[pi].z = 0; ld[pi].w = 1; }
+#else
+                        ld[pi] = dv::ld_global(reinterpret_cast<const piece_t *>(prow + (pc << 6)));
+#endif
+                    }
+#pragma unroll
+                    for (int pi = 0; pi < NPI; pi++) {
+                        uint4 v;
+                        if constexpr (HBD) v = ld[pi];
+                        else v = make_uint4(__builtin_amdgcn_perm(0u, ld[pi].x, 0x0c010c00u), __builtin_amdgcn_perm(0u, ld[pi].x, 0x0c030c02u),
+                                            __builtin_amdgcn_perm(0u, ld[pi].y, 0x0c010c00u), __builtin_amdgcn_perm(0u, ld[pi].y, 0x0c030c02u));
+                        *reinterpret_cast<uint4 *>(win + wr * WS + 8 * (lp + pi * PG)) = v;
+                    }
+                }
+            } else {
             piece_t ld[NRI][NPI];
             bool ok[NRI][NPI];
 #pragma unroll
@@ -175,6 +210,39 @@ __device__ __forceinline__ void mc_gather(const McRef rf, const McPred &pd, cons
                                         __builtin_amdgcn_perm(0u, ld[ri][pi].y, 0x0c010c00u), __builtin_amdgcn_perm(0u, ld[ri][pi].y, 0x0c030c02u));
                     *reinterpret_cast<uint4 *>(win + wr * WS + 8 * pc) = v;
                 }
+            }
+        } else if constexpr (ONE_ROW) {
+            // Edge emulation on the same grid: the lane's row is the picture's nearest (clamped once, not per pixel), and of its pieces —
+            // aligned to 8 columns like the tiles — those that lie inside the picture's columns are fetched whole, as above.  Only a piece
+            // that hangs over the left or the right edge (or lies beyond it) takes its 8 pixels one by one at clamped columns.  Rows and
+            // pieces the taps do not reach are left out as above (the per-pixel form below fills the whole window: 25 instructions per pixel).
+            const int wr = R0 + lr, y = y0 + wr;
+            if (lr < NR && wr >= row_lo && wr < row_hi) {
+                const int sy = dv::clamp3(y, 0, rh - 1);
+                const pixel *prow = src + (dv::mul_i24(sy & ~7, rs) + ((sy & 7) << 3));
+                const int p_lo = (c_first - xa) >> 3, p_hi = (c_last - xa) >> 3;
+                // (a piece is stored before the next is fetched: the 8-bit 8x8 pairs spill at 72 registers with three pieces in flight, and this path is rare)
+#pragma unroll
+                for (int pi = 0; pi < NPI; pi++) {
+                    uint4 v;
+                    const int x = xa + 8 * dv::clamp3(lp + pi * PG, p_lo, p_hi);
+                    if (x >= 0 && x + 7 < rw) {
+                        const piece_t ld = dv::ld_global(reinterpret_cast<const piece_t *>(prow + (x << 3)));
+                        if constexpr (HBD) v = ld;
+                        else v = make_uint4(__builtin_amdgcn_perm(0u, ld.x, 0x0c010c00u), __builtin_amdgcn_perm(0u, ld.x, 0x0c030c02u),
+                                                __builtin_amdgcn_perm(0u, ld.y, 0x0c010c00u), __builtin_amdgcn_perm(0u, ld.y, 0x0c030c02u));
+                    } else {
+                        uint32_t px[8];
+#pragma unroll
+                        for (int e = 0; e < 8; e++) {
+                            const int sx = dv::clamp3(x + e, 0, rw - 1);
+                            px[e] = (uint32_t) dv::ld_global(prow + (((sx >> 3) << 6) + (sx & 7)));
+                        }
+                        v = make_uint4(px[0] | (px[1] << 16), px[2] | (px[3] << 16), px[4] | (px[5] << 16), px[6] | (px[7] << 16));
+                    }
+                    *reinterpret_cast<uint4 *>(win + wr * WS + 8 * (lp + pi * PG)) = v;
+                }
+            }
         } else {
             // edge emulation through the tile addressing: per-pixel clamped fetch, 8 independent loads in flight per lane
             for (int i0 = l; i0 < WRG * WS; i0 += 8 * LPT) {
@@ -272,6 +340,9 @@ __device__ __forceinline__ void mc_hpass(const McPred &pd, const Taps &fh, const
     const int sh1 = fbits - ib;
     const int rnd1 = (1 << sh1) >> 1;
     // the four sums of one 4-pixel strip of one window row (rounding offset included)
+    // (a sum's first link takes the rounding offset as its third operand, dv::dot2_seed; the taps of a one-tile wave are scalars)
+    constexpr bool UNI = S::G == 1;
+    auto dot = [&](const bool first, const uint32_t a, const uint32_t b, const int c) { return first ? dv::dot2_seed<UNI>(a, b, rnd1) : dv::dot2(a, b, c); };
     auto row_sums = [&](const int row, const int s, int (&o)[4]) {
         const uint2 *wp = reinterpret_cast<const uint2 *>(win + row * WS + 4 * s);
         int s0 = rnd1, s1 = rnd1, s2 = rnd1, s3 = rnd1;
@@ -299,14 +370,14 @@ __device__ __forceinline__ void mc_hpass(const McPred &pd, const Taps &fh, const
                 const uint32_t d[6] = { dw[0], dw[1], dw[2], dw[3], dw[4], dw[5] };
                 if (!(toff & 1)) {
 #pragma unroll
-                    for (int k = 0; k < 4; k++) { s0 = dv::dot2(d[k], fh.ev[k], s0); s2 = dv::dot2(d[k + 1], fh.ev[k], s2); }
+                    for (int k = 0; k < 4; k++) { s0 = dot(k == 0, d[k], fh.ev[k], s0); s2 = dot(k == 0, d[k + 1], fh.ev[k], s2); }
 #pragma unroll
-                    for (int k = 0; k < 5; k++) { s1 = dv::dot2(d[k], fh.od[k], s1); s3 = dv::dot2(d[k + 1], fh.od[k], s3); }
+                    for (int k = 0; k < 5; k++) { s1 = dot(k == 0, d[k], fh.od[k], s1); s3 = dot(k == 0, d[k + 1], fh.od[k], s3); }
                 } else {
 #pragma unroll
-                    for (int k = 0; k < 5; k++) { s0 = dv::dot2(d[k], fh.od[k], s0); s2 = dv::dot2(d[k + 1], fh.od[k], s2); }
+                    for (int k = 0; k < 5; k++) { s0 = dot(k == 0, d[k], fh.od[k], s0); s2 = dot(k == 0, d[k + 1], fh.od[k], s2); }
 #pragma unroll
-                    for (int k = 0; k < 4; k++) { s1 = dv::dot2(d[k + 1], fh.ev[k], s1); s3 = dv::dot2(d[k + 2], fh.ev[k], s3); }
+                    for (int k = 0; k < 4; k++) { s1 = dot(k == 0, d[k + 1], fh.ev[k], s1); s3 = dot(k == 0, d[k + 2], fh.ev[k], s3); }
                 }
             }
         } else if constexpr (NARROW) {
@@ -379,7 +450,8 @@ __device__ __forceinline__ void mc_vpass(const McPred &pd, const Taps &fv, const
     const int fbits = pd.fbits;
     // pixels: (sum + rnd) >> (fbits + ib), src/mc_tmpl.c:157-159, 176-178; intermediates of a compound: (sum + rnd) >> fbits, less the bias, :272-277, 294-299
     const int sh2 = as_prep ? fbits : fbits + ib, vb = as_prep ? bias : 0;
-    const int rnd2 = (1 << sh2) >> 1;
+    // (the bias leaves with the rounding offset: ((sum + rnd) >> sh) - vb == (sum + rnd - (vb << sh)) >> sh, the shift being arithmetic)
+    const int rnd2 = ((1 << sh2) >> 1) - (vb << sh2);
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const int it = r * LPT + l;
@@ -388,18 +460,22 @@ __device__ __forceinline__ void mc_vpass(const McPred &pd, const Taps &fv, const
         const int j0 = vr >> 1;
         const bool odd = vr & 1;
         int sum[4] = { rnd2, rnd2, rnd2, rnd2 };
+        auto dot = [&](const bool first, const uint32_t a, const uint32_t b, const int c) { return first ? dv::dot2_seed<false>(a, b, rnd2) : dv::dot2(a, b, c); };
 #pragma unroll
         for (int k = 0; k < 5; k++) {
             const uint32_t g = odd ? fv.od[k] : (k < 4 ? fv.ev[k] : 0u);
-            const int j = dv::imin(j0 + k, NPR - 1);     // the 5th pair of an even row is weight 0
+            // (the 5th pair of an even row is weight 0.  vr < TH, so j0 + 4 <= TH / 2 + 3 = NPR - 1: the five pairs are one address and
+            // constant offsets, no clamp)
+            static_assert((TH - 1) / 2 + 4 <= NPR - 1, "the pairs a row reads lie inside the intermediate");
+            const int j = j0 + k;
             const uint4 m = *reinterpret_cast<const uint4 *>(mid + j * TW + 4 * vs);
-            sum[0] = dv::dot2(m.x, g, sum[0]);
-            sum[1] = dv::dot2(m.y, g, sum[1]);
-            sum[2] = dv::dot2(m.z, g, sum[2]);
-            sum[3] = dv::dot2(m.w, g, sum[3]);
+            sum[0] = dot(k == 0, m.x, g, sum[0]);
+            sum[1] = dot(k == 0, m.y, g, sum[1]);
+            sum[2] = dot(k == 0, m.z, g, sum[2]);
+            sum[3] = dot(k == 0, m.w, g, sum[3]);
         }
 #pragma unroll
-        for (int x = 0; x < 4; x++) q[r][x] = (sum[x] >> sh2) - vb;
+        for (int x = 0; x < 4; x++) q[r][x] = sum[x] >> sh2;
     }
 }
 
@@ -421,7 +497,7 @@ template <int TW, int TH, typename pixel, bool TO_LDS = false, bool TILED = fals
 __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs, const int n_refs, const McTile *__restrict__ tiles, const int t0, const int nt,
                                         int16_t *__restrict__ prep, const int bitdepth_max, uint4 *smem,
                                         pixel *pred_s = nullptr, const int pred_tile0 = 0, const int pred_tpb_log2 = 0,
-                                        const int pred_w = 0, const int pred_h = 0, const DevPlanes &twin = DevPlanes())
+                                        const int pred_w = 0, const int pred_h = 0, const bool stage_refs = true, const DevPlanes &twin = DevPlanes())
 {
     constexpr int NS = TW / 4;                          // 4-pixel strips per row
     constexpr int LPT = mc_cmin(64, TW * TH / 4);       // lanes per tile
@@ -468,16 +544,34 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
         uint32_t *const rec_s = reinterpret_cast<uint32_t *>(win_s);      // (dead until the gather: every lane has its record in registers first)
         const uint32_t *recs = reinterpret_cast<const uint32_t *>(tiles + t0);
         const int nw = nt * RW;
-        for (int i = lane; i < nw; i += 64) rec_s[i] = recs[i];
+        // (at most G records: a fixed number of rounds.  Every load of the hand-off — the records' and the reference table's below — is issued, at an
+        // index held inside what is there, before the first store: one trip to memory, not one per round)
+        constexpr int NRR = (G * RW + 63) / 64, NRT = (int) sizeof(RefSet) / 4 / 64;
+        uint32_t rv[NRR] = {}, tv[NRT] = {};
+        if (nw > 0) {           // (wave-uniform)
+#pragma unroll
+            for (int k = 0; k < NRR; k++) rv[k] = dv::ld_global(recs + dv::imin(lane + 64 * k, nw - 1));
+        }
         // the reference plane table goes to LDS in the same round trip: the lanes index it by their own tile's reference,
         // and a second, dependent trip to the kernel arguments would sit in front of every window fetch
         uint32_t *const ref_s = mid_s + G * NPRA * TW + SL;
         // (only the n_refs entries the call has: no record names another — the callers check — and the table's other slots are never read)
         const uint32_t *rsrc = reinterpret_cast<const uint32_t *>(&refs);
         const int nrw = n_refs * (int) (sizeof(DevPlanes) / 4);
+        // (stage_refs: wave-uniform.  The paired kernels call this body several times per wave; the table is the same in every call and nothing
+        // else is stored behind the intermediates, so only the wave's first call copies it)
+        if (stage_refs) {
 #pragma unroll
-        for (int i = 0; i < (int) sizeof(RefSet) / 4; i += 64)
-            if (i + lane < nrw) ref_s[i + lane] = rsrc[i + lane];
+            for (int k = 0; k < NRT; k++) tv[k] = rsrc[dv::imin(lane + 64 * k, dv::imax(nrw, 1) - 1)];
+        }
+#pragma unroll
+        for (int k = 0; k < NRR; k++)
+            if (lane + 64 * k < nw) rec_s[lane + 64 * k] = rv[k];
+        if (stage_refs) {
+#pragma unroll
+            for (int k = 0; k < NRT; k++)
+                if (lane + 64 * k < nrw) ref_s[lane + 64 * k] = tv[k];
+        }
         dv::wave_sync();
         const uint32_t *rp = rec_s + (live ? sub : 0) * RW;
         uint32_t *tw_ = reinterpret_cast<uint32_t *>(&t);
@@ -498,7 +592,10 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
 #else
     const bool compound = live && (t.kind == MCT_AVG || t.kind == MCT_WAVG);
 #endif
-    const bool as_prep = t.kind != MCT_PUT && t.kind != MCT_PUT_TMP;   // PREP and both inputs of a compound tile
+    // TO_LDS: the lists of the paired kernels hold PUT, AVG and WAVG tiles only, every one a whole TW x TH (a prediction block is paired with the
+    // transform block of its own rectangle, api_lists.hip): no arena destination, no partial strip, nothing of either worked out or tested for
+    const bool is_prep = !TO_LDS && t.kind == MCT_PREP, is_tmp = !TO_LDS && t.kind == MCT_PUT_TMP;
+    const bool as_prep = t.kind != MCT_PUT && !is_tmp;   // PREP and both inputs of a compound tile
 
     int acc0[R][4], q[R][4];
 #pragma unroll
@@ -585,13 +682,13 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
             }
         }
     };
-    if (TWIN && live && t.kind != MCT_PREP && t.kind != MCT_PUT_TMP) dv::off_to_xy(t.dst_off, tstride, tbx, tby);
+    if (TWIN && live && !is_prep && !is_tmp) dv::off_to_xy(t.dst_off, tstride, tbx, tby);
     if (live) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int it = r * LPT + l;
             const int vr = it / NS, vs = it % NS;
-            if (vr >= t.h) continue;
+            if (!TO_LDS && vr >= t.h) continue;
             int o[4];
             if (t.kind == MCT_AVG) {
 #pragma unroll
@@ -604,13 +701,13 @@ __device__ __forceinline__ void mc_body(const DevPlanes &dst, const RefSet &refs
 #pragma unroll
                 for (int x = 0; x < 4; x++) o[x] = q[r][x];
             }
-            const int nvalid = dv::imin(4, t.w - 4 * vs);
-            if (t.kind != MCT_PREP) {
+            const int nvalid = TO_LDS ? 4 : dv::imin(4, t.w - 4 * vs);
+            if (!is_prep) {
 #pragma unroll
                 for (int x = 0; x < 4; x++) o[x] = dv::clamp3(o[x], 0, bitdepth_max);
                 // PUT_TMP: pixels into the scratch arena, row stride = block width (the reference's `lap` buffer of obmc())
                 // TWIN with twin.tiled == 2: the picture lives in its twin only (DAV1D_HIP_TWIN_ONLY) — nothing goes to the raster planes
-                if (t.kind == MCT_PUT_TMP) {
+                if (is_tmp) {
                     put_strip(reinterpret_cast<pixel *>(prep) + t.dst_off + (t.oy + vr) * t.bw + t.ox + 4 * vs, o, nvalid, std::true_type());
                 } else if constexpr (TO_LDS) {
                     put_strip(pred_s + ((ti - pred_tile0) >> pred_tpb_log2) * (pred_w * (pred_h + 1)) + (t.oy + vr) * pred_w + t.ox + 4 * vs, o, nvalid, std::false_type());

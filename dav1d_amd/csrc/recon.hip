@@ -86,7 +86,7 @@ void recon_fused_kernel(const DevPlanes dst, const RefSet refs, const int n_refs
     if constexpr (NW == 1) {
         for (int c = 0; c < ntile; c += G) {
             mc_body<TW, TH, pixel, true, TILED>(dst, refs, n_refs, tiles, tile0 + c, dv::imin(G, ntile - c), prep, bitdepth_max, smem_mc,
-                                         pred, tile0, rc_log2(TPB), W, W);
+                                         pred, tile0, rc_log2(TPB), W, W, c == 0);
             dv::wave_sync();
         }
     } else {

@@ -6,7 +6,8 @@ cd "$ROOT"
 cp dav1d_amd/libdav1d_hip.so /tmp/libdav1d_hip_tree.so
 for v in "$@"; do
     if [ -n "$v" ]; then cp "dav1d_amd/build/variants/$v" dav1d_amd/libdav1d_hip.so; else cp /tmp/libdav1d_hip_tree.so dav1d_amd/libdav1d_hip.so; fi
-    timeout 200 python bench.py --full --no-cpu --no-e2e --no-c1 --no-full $AB_ARGS > /tmp/ab.json 2> /tmp/ab.err || { echo "[$v] FAILED: $(tail -3 /tmp/ab.err)"; continue; }
+    # (a run that fails or is ended by its time limit ends the script: nothing more is started on that device)
+    timeout -k 10 200 python bench.py --full --no-cpu --no-e2e --no-c1 --no-full $AB_ARGS > /tmp/ab.json 2> /tmp/ab.err || { rc=$?; echo "[$v] FAILED ($rc): $(tail -3 /tmp/ab.err)"; cp /tmp/libdav1d_hip_tree.so dav1d_amd/libdav1d_hip.so; exit $rc; }
     python - "$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

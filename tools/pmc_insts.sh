@@ -2,6 +2,7 @@
 # Instructions per wave, by kind, of the step's kernels (one rocprofv3 --pmc pass per variant library over tools/layout_sweep.py): with the
 # knock-out variants of tools/knockout.sh the differences say how many instructions each part of a wave's program costs.
 #   tools/pmc_insts.sh <variant.so> ...      -> gpurun_out/insts_<variant>.txt
+# A run that fails or is ended by its time limit ends the script: nothing more is started on that device.
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$ROOT/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
@@ -10,8 +11,10 @@ for lib in "$@"; do
     tag=$(basename "$lib" .so)
     OUT=/tmp/pmc_$tag
     rm -rf "$OUT"
-    timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT" -- \
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT" -- \
         python "$ROOT/tools/layout_sweep.py" --no-raster --steps 2 --lib "$ROOT/$lib" ${SWEEP_SETS:+--sets $SWEEP_SETS} > "$ROOT/gpurun_out/insts_$tag.log" 2>&1
+    rc=$?
+    if [ $rc -ne 0 ]; then echo "pmc_insts: $lib failed with status $rc (insts_$tag.log)"; exit $rc; fi
     python - "$OUT" > "$ROOT/gpurun_out/insts_$tag.txt" <<'PY'
 import csv, glob, collections, re, sys
 d = collections.defaultdict(lambda: collections.defaultdict(list))
