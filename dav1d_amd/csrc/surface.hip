@@ -7,7 +7,7 @@
 // tiles of the twin (eight 128-byte lines, each lane its 16 bytes) or eight 128-byte pieces of raster rows, a store leaves eight pieces of
 // 128 consecutive bytes of destination rows (256 where a lane leaves 32: interleaved chroma, float samples).  Both sides are whole memory lines when
 // the destination rows start on one; no line is requested twice.
-#include "surface_common.h"
+#include "surface_call.h"
 
 namespace {
 
@@ -120,22 +120,6 @@ int launch_surface(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, c
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes, const int row0, const int row1)
-{
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) {
-        OutF32 o; o.scale = (float) (1.0 / (double) ((1 << src->bpc) - 1));
-        return launch_surface<pixel, TILED, OutF32>(c, dst, src, planes, row0, row1, o);
-    }
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst->sample == DAV1D_HIP_SAMPLE_MSB16) {
-            OutMsb16 o; o.shift = 16 - src->bpc;
-            return launch_surface<pixel, TILED, OutMsb16>(c, dst, src, planes, row0, row1, o);
-        }
-    }
-    return launch_surface<pixel, TILED, OutNative<pixel>>(c, dst, src, planes, row0, row1, OutNative<pixel>());
-}
-
 } // namespace
 
 extern "C" int dav1d_hip_surface_export(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, int row0, int row1)
@@ -146,11 +130,11 @@ extern "C" int dav1d_hip_surface_export(Dav1dHipContext *c, const Dav1dHipSurfac
     const bool tiled = call.tiled;
     void *const *const planes = call.planes;
     if (row1 <= row0) return 0;
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc;
-    if (src->bpc == 8) rc = tiled ? launch_sample<uint8_t, true>(c, dst, src, planes, row0, row1) : launch_sample<uint8_t, false>(c, dst, src, planes, row0, row1);
-    else rc = tiled ? launch_sample<uint16_t, true>(c, dst, src, planes, row0, row1) : launch_sample<uint16_t, false>(c, dst, src, planes, row0, row1);
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    const CallTimer t(c);
+    return t.done(with_pixel_state(src->bpc, tiled, [&](auto px, auto state) {
+        typedef decltype(px) pixel;
+        return with_out<pixel>(dst->sample, src->bpc, [&](const auto &out) {
+            return launch_surface<pixel, decltype(state)::value>(c, dst, src, planes, row0, row1, out);
+        });
+    }));
 }

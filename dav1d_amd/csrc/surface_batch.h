@@ -1,7 +1,9 @@
-// The batched scaled tensor-ready export behind its two entry points (surface_batch.hip has the account of the table, the search, the picture
-// states and the staging ring; surface_resize.hip runs the same from its own entry point, with the body that lets an axis go up).
+// What the batched exports share (surface_batch.hip has the account of the table, the search, the picture states and the staging ring): the kernels of
+// the scaled and resized batches, and the host side of every batch — the front of an entry point (batch_plans), the plans it keeps (take_plans) and the
+// table of a launch from its staging slot to the events behind it (BatchTable).  surface_resize.hip, surface_reduce.hip and
+// surface_colour_reduce.hip run their batches through the same.
 #pragma once
-#include "surface_common.h"
+#include "surface_call.h"
 
 namespace {
 
@@ -27,38 +29,40 @@ template <typename P> __device__ __forceinline__ P *in_device_memory(P *const p)
 #endif
 }
 
+// the item of workgroup g: the last k with first[k] <= g, of a prefix with first[0] = 0 and first[n] = all workgroups
+__device__ __forceinline__ int item_of(const uint32_t *const first, const int n, const uint32_t g)
+{
+    int lo = 0, hi = n;          // first[lo] <= g < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 template <typename pixel, bool TILED, typename Out>
 __global__ __launch_bounds__(256) void surface_scale_rgbx_batch_kernel(const BatchItem<Out> *const __restrict__ items, const uint32_t *const __restrict__ first,
                                                                        const int n)
 {
     __shared__ ScaleLds<pixel> L;
     const uint32_t g = blockIdx.x;
-    int lo = 0, hi = n;          // first[lo] <= g < first[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    const int lo = item_of(first, n, g);
     const BatchItem<Out> &it = items[lo];
     ScaleRgbxArgs a = it.a;
     for (int pl = 0; pl < 3; pl++) { a.pl[pl].s = in_device_memory(a.pl[pl].s); a.c.d[pl] = in_device_memory(a.c.d[pl]); }
     scale_rgbx_cell<pixel, TILED, Out>(L, a, (int) (g - first[lo]), it.out);
 }
 
-// the same search in front of the resizing body (surface_resize.hip: an axis of an item may go up); a kernel of its own, so that the one above
-// keeps its code to the register
+// the same search in front of the resizing body (surface_resize.hip: an axis of an item may go up; surface_reduce.hip: Q at its own size); a kernel of
+// its own, so that the one above keeps its code to the register
 template <typename pixel, bool TILED, typename Out>
 __global__ __launch_bounds__(256, sizeof(pixel) == 1 ? 5 : 4) void surface_resize_rgbx_batch_kernel(const BatchItem<Out> *const __restrict__ items, const uint32_t *const __restrict__ first,
                                                                         const int n)
 {
     __shared__ ScaleLds<pixel> L;
     const uint32_t g = blockIdx.x;
-    int lo = 0, hi = n;          // first[lo] <= g < first[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= g) lo = mid;
-        else hi = mid;
-    }
+    const int lo = item_of(first, n, g);
     const BatchItem<Out> &it = items[lo];
     ScaleRgbxArgs a = it.a;
     for (int pl = 0; pl < 3; pl++) { a.pl[pl].s = in_device_memory(a.pl[pl].s); a.c.d[pl] = in_device_memory(a.c.d[pl]); }
@@ -66,6 +70,46 @@ __global__ __launch_bounds__(256, sizeof(pixel) == 1 ? 5 : 4) void surface_resiz
 }
 
 // ---- the host side
+
+inline size_t round_up(const size_t v, const size_t a) { return (v + a - 1) / a * a; }
+
+// the plans of a call live in the context's batch_plan (it grows to the largest batch); nullptr: no memory
+template <typename Plan> Plan *take_plans(Dav1dHipContext *const c, const int n)
+{
+    try {
+        if (c->batch_plan.size() < (size_t) n * sizeof(Plan) + alignof(Plan)) c->batch_plan.resize((size_t) n * sizeof(Plan) + alignof(Plan));
+    } catch (...) {
+        return nullptr;
+    }
+    return (Plan *) round_up((size_t) (uintptr_t) c->batch_plan.data(), alignof(Plan));
+}
+
+// The front of a batch entry point, in the order the header promises: the count; `whole_rc`, what the call as a whole refuses (its filter, a missing
+// handle); the empty batch; the arrays; then per item check(i, plan) — the family's checks and pictures_on_device — and the rule of one kernel
+// instance for the batch: format and sample are item 0's, and with `same_pixel` the pixel size (the colour-managed batch checks the depth itself, against
+// its handle).  *plans: the checked plans, nullptr where there is nothing to run (the call then returns what this returns).
+template <typename Plan, typename Check>
+int batch_plans(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src, const int whole_rc,
+                const bool same_pixel, int *const bad_item, Plan **const plans, Check &&check)
+{
+    *plans = nullptr;
+    if (bad_item) *bad_item = -1;
+    if (!c || n < 0 || n > DAV1D_HIP_SURFACE_BATCH_MAX) return -EINVAL;
+    if (whole_rc) return whole_rc;
+    if (!n) return 0;
+    if (!dst || !src) return -EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!src[i]) { if (bad_item) *bad_item = i; return -EINVAL; }
+    Plan *const plan = take_plans<Plan>(c, n);
+    if (!plan) return -ENOMEM;
+    for (int i = 0; i < n; i++) {
+        int rc = check(i, plan[i]);
+        if (!rc && (dst[i].format != dst[0].format || dst[i].sample != dst[0].sample || (same_pixel && (src[i]->bpc == 8) != (src[0]->bpc == 8)))) rc = -EINVAL;
+        if (rc) { if (bad_item) *bad_item = i; return rc; }
+    }
+    *plans = plan;
+    return 0;
+}
 
 // a staging slot of at least `bytes`, free to be written: the one used longest ago, waited for if its batch has not run yet
 inline int batch_stage_take(Dav1dHipContext *const c, const size_t bytes, Dav1dHipContext::BatchStage **const out)
@@ -95,100 +139,134 @@ inline int batch_stage_take(Dav1dHipContext *const c, const size_t bytes, Dav1dH
     return 0;
 }
 
-template <typename pixel, typename Out, bool RESIZE>
-int export_batch(Dav1dHipContext *const c, const int n, const int n_raster, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src,
-                 const BatchPlan *const plan, const Dav1dHipRgbParams &p)
-{
-    typedef BatchItem<Out> Item;
-    // records: the raster items, then the twin-only ones; behind them the two prefixes
-    const size_t first_at = (size_t) n * sizeof(Item), bytes = first_at + (size_t) (n + 2) * sizeof(uint32_t);
+// The table of a batched launch, from its staging slot to the events behind the launches.  The items are sorted by class (cls(i) < NCLS: the kernel
+// instance that exports item i), each class with a prefix of its own:
+//     [ items of class 0, 1, .. | first: n_cls[0] + 1 words, n_cls[1] + 1 words, .. | extra, from a multiple of 16 bytes ]
+// open, fill, run, in that order; whatever the caller puts into extra() goes between open and run.
+template <typename Item, int NCLS, typename Classify> struct BatchTable {
+    Dav1dHipContext *const c;
+    const int n;
+    const Classify cls;
     Dav1dHipContext::BatchStage *s;
-    if (const int rc = batch_stage_take(c, bytes, &s)) return rc;
-    Item *const items = (Item *) s->host;
-    uint32_t *const first = (uint32_t *) (s->host + first_at);
-    const int n_slice[2] = { n_raster, n - n_raster }, slice0[2] = { 0, n_raster }, first0[2] = { 0, n_raster + 1 };
-    int fill[2] = { 0, 0 };
-    uint32_t groups[2] = { 0, 0 };
-    for (int i = 0; i < n; i++) {
-        const SurfaceCall &call = plan[i].call;
-        const ScaleGeom &g = plan[i].g;
-        const int t = call.tiled, k = fill[t]++;
-        Item &it = items[slice0[t] + k];
-        unsigned ng;
-        it.a = t ? make_scale_rgbx_args<pixel, true, typename Out::T>(&dst[i], src[i], call.planes, g, p, call.row0, call.row1, &ng)
-                 : make_scale_rgbx_args<pixel, false, typename Out::T>(&dst[i], src[i], call.planes, g, p, call.row0, call.row1, &ng);
-        it.out = Out();
-        set_out(it.out, p, src[i]->bpc);
-        first[first0[t] + k] = groups[t];
-        groups[t] += ng;
+    size_t first_at, extra_at, bytes;
+    int n_cls[NCLS], slice0[NCLS], first0[NCLS];
+
+    Item *items() const { return (Item *) s->host; }
+    uint32_t *first() const { return (uint32_t *) (s->host + first_at); }
+    uint8_t *extra() const { return s->host + extra_at; }
+
+    int open(const size_t extra_bytes)
+    {
+        for (int t = 0; t < NCLS; t++) n_cls[t] = 0;
+        for (int i = 0; i < n; i++) n_cls[cls(i)]++;
+        for (int t = 0, at = 0; t < NCLS; at += n_cls[t++]) { slice0[t] = at; first0[t] = at + t; }
+        first_at = (size_t) n * sizeof(Item);
+        extra_at = first_at + (size_t) (n + NCLS) * sizeof(uint32_t);
+        if (extra_bytes) extra_at = round_up(extra_at, 16);
+        bytes = extra_at + extra_bytes;
+        return batch_stage_take(c, bytes, &s);
     }
-    for (int t = 0; t < 2; t++) first[first0[t] + n_slice[t]] = groups[t];
-    HIP_TRY(hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, c->stream));
-    const Item *const d_items = (const Item *) s->dev;
-    const uint32_t *const d_first = (const uint32_t *) (s->dev + first_at);
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc = 0;
-    if (n_slice[0]) {
-        if constexpr (RESIZE) hipLaunchKernelGGL((surface_resize_rgbx_batch_kernel<pixel, false, Out>), dim3(groups[0]), dim3(256), 0, c->stream, d_items, d_first, n_slice[0]);
-        else hipLaunchKernelGGL((surface_scale_rgbx_batch_kernel<pixel, false, Out>), dim3(groups[0]), dim3(256), 0, c->stream, d_items, d_first, n_slice[0]);
-        rc = hip_rc(hipGetLastError());
+    // fill(i, class, item) writes the record of item i and returns what it counts, workgroups or cells; returns the count of all
+    template <typename Fill> unsigned fill(Fill &&fill)
+    {
+        int k[NCLS] = {};
+        unsigned total = 0;
+        for (int i = 0; i < n; i++) {
+            const int t = cls(i), at = k[t]++;
+            const unsigned count = fill(i, t, items()[slice0[t] + at]);
+            first()[first0[t] + at] = count;
+            total += count;
+        }
+        return total;
     }
-    if (n_slice[1] && !rc) {
-        if constexpr (RESIZE) hipLaunchKernelGGL((surface_resize_rgbx_batch_kernel<pixel, true, Out>), dim3(groups[1]), dim3(256), 0, c->stream, d_items + slice0[1], d_first + first0[1],
-                                                 n_slice[1]);
-        else hipLaunchKernelGGL((surface_scale_rgbx_batch_kernel<pixel, true, Out>), dim3(groups[1]), dim3(256), 0, c->stream, d_items + slice0[1], d_first + first0[1],
-                                n_slice[1]);
-        rc = hip_rc(hipGetLastError());
+    // The prefixes (a workgroup per `per` of what an item counted), the upload, and between the timing events before(extra on the device) and
+    // launch(class, its items, its prefix, its items' number, its workgroups) for every class that has any; the slot is busy until they ran.
+    template <typename Before, typename Launch> int run(const unsigned per, Before &&before, Launch &&launch)
+    {
+        uint32_t groups[NCLS];
+        for (int t = 0; t < NCLS; t++) {
+            uint32_t *const f = first() + first0[t];
+            groups[t] = 0;
+            for (int j = 0; j < n_cls[t]; j++) {
+                const uint32_t ng = (f[j] + per - 1) / per;
+                f[j] = groups[t];
+                groups[t] += ng;
+            }
+            f[n_cls[t]] = groups[t];
+        }
+        HIP_TRY(hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, c->stream));
+        const CallTimer timer(c);
+        int rc = before((const uint8_t *) s->dev + extra_at);
+        for (int t = 0; t < NCLS; t++) {
+            if (!groups[t] || rc) continue;
+            launch(t, (const Item *) s->dev + slice0[t], (const uint32_t *) (s->dev + first_at) + first0[t], n_cls[t], groups[t]);
+            rc = hip_rc(hipGetLastError());
+        }
+        timer.done(rc);
+        (void) hipEventRecord(s->done, c->stream);
+        s->busy = true;
+        return rc;
     }
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    (void) hipEventRecord(s->done, c->stream);
-    s->busy = true;
-    c->last_ms_pending = !rc;
-    return rc;
+};
+template <typename Item, int NCLS, typename Classify> BatchTable<Item, NCLS, Classify> batch_table(Dav1dHipContext *const c, const int n, const Classify cls)
+{
+    return BatchTable<Item, NCLS, Classify>{ c, n, cls };
 }
 
-template <typename pixel, bool RESIZE>
-int export_batch_sample(Dav1dHipContext *const c, const int n, const int n_raster, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src,
-                        const BatchPlan *const plan, const Dav1dHipRgbParams &p)
+// the record of an item of the scaled, resized and reduced batches, and its workgroups
+template <typename pixel, typename Out>
+unsigned rgbx_item_fill(BatchItem<Out> &it, const bool tiled, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
+                        const ScaleGeom &g, const Dav1dHipRgbParams &p, const int row0, const int row1)
 {
-    if (dst[0].sample == DAV1D_HIP_SAMPLE_F32) return export_batch<pixel, RgbF32, RESIZE>(c, n, n_raster, dst, src, plan, p);
-    if (dst[0].sample == DAV1D_HIP_SAMPLE_F16) return export_batch<pixel, RgbF16, RESIZE>(c, n, n_raster, dst, src, plan, p);
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst[0].sample == DAV1D_HIP_SAMPLE_MSB16) return export_batch<pixel, RgbInt<OutMsb16>, RESIZE>(c, n, n_raster, dst, src, plan, p);
+    unsigned ng;
+    it.a = tiled ? make_scale_rgbx_args<pixel, true, typename Out::T>(dst, src, planes, g, p, row0, row1, &ng)
+                 : make_scale_rgbx_args<pixel, false, typename Out::T>(dst, src, planes, g, p, row0, row1, &ng);
+    it.out = Out();
+    set_out(it.out, p, src->bpc);
+    return ng;
+}
+
+// ... and the launch of a class of them: raster sources, or twin-only ones
+template <typename pixel, typename Out, bool RESIZE>
+void launch_rgbx_batch(hipStream_t st, const bool tiled, const BatchItem<Out> *const items, const uint32_t *const first, const int n, const uint32_t groups)
+{
+    const dim3 grid(groups), wg(256);
+    if constexpr (RESIZE) {
+        if (tiled) hipLaunchKernelGGL((surface_resize_rgbx_batch_kernel<pixel, true, Out>), grid, wg, 0, st, items, first, n);
+        else hipLaunchKernelGGL((surface_resize_rgbx_batch_kernel<pixel, false, Out>), grid, wg, 0, st, items, first, n);
+    } else {
+        if (tiled) hipLaunchKernelGGL((surface_scale_rgbx_batch_kernel<pixel, true, Out>), grid, wg, 0, st, items, first, n);
+        else hipLaunchKernelGGL((surface_scale_rgbx_batch_kernel<pixel, false, Out>), grid, wg, 0, st, items, first, n);
     }
-    return export_batch<pixel, RgbInt<OutNative<pixel>>, RESIZE>(c, n, n_raster, dst, src, plan, p);
 }
 
 // dav1d_hip_surface_export_rgb_scaled_batch (RESIZE false) and dav1d_hip_surface_export_rgb_resized_batch (true: an item may go up)
 template <bool RESIZE>
 int export_batch_call(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src,
-                      const Dav1dHipSurfaceRect *const crop, const Dav1dHipRgbParams *const params, int *const bad_item)
+                      const Dav1dHipSurfaceRect *const crop, const Dav1dHipRgbParams *const params, const int whole_rc, int *const bad_item)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
-    if (bad_item) *bad_item = -1;
-    if (!c || n < 0 || n > DAV1D_HIP_SURFACE_BATCH_MAX) return -EINVAL;
-    if (!n) return 0;
-    if (!dst || !src) return -EINVAL;
-    for (int i = 0; i < n; i++)
-        if (!src[i]) { if (bad_item) *bad_item = i; return -EINVAL; }
-    try {
-        if (c->batch_plan.size() < (size_t) n * sizeof(BatchPlan)) c->batch_plan.resize((size_t) n * sizeof(BatchPlan));
-    } catch (...) {
-        return -ENOMEM;
-    }
-    BatchPlan *const plan = (BatchPlan *) c->batch_plan.data();
-    int n_raster = 0;
-    for (int i = 0; i < n; i++) {
-        SurfaceCall &call = plan[i].call;
-        int rc = rgbx_scaled_args_check(&dst[i], src[i], crop ? &crop[i] : nullptr, p, 0, dst[i].h, &call, &plan[i].g, RESIZE);
-        if (!rc) rc = pictures_on_device(c, src[i], 1);
-        // one kernel instance for the batch: format, sample and pixel size are item 0's
-        if (!rc && (dst[i].format != dst[0].format || dst[i].sample != dst[0].sample || (src[i]->bpc == 8) != (src[0]->bpc == 8))) rc = -EINVAL;
-        if (rc) { if (bad_item) *bad_item = i; return rc; }
-        n_raster += !call.tiled;
-    }
-    return src[0]->bpc == 8 ? export_batch_sample<uint8_t, RESIZE>(c, n, n_raster, dst, src, plan, p) : export_batch_sample<uint16_t, RESIZE>(c, n, n_raster, dst, src, plan, p);
+    const Dav1dHipRgbParams p = rgb_params_of(params);
+    BatchPlan *plan;
+    const int rc = batch_plans(c, n, dst, src, whole_rc, true, bad_item, &plan, [&](const int i, BatchPlan &pl) {
+        const int rc = rgbx_scaled_args_check(&dst[i], src[i], crop ? &crop[i] : nullptr, p, 0, dst[i].h, &pl.call, &pl.g, RESIZE);
+        return rc ? rc : pictures_on_device(c, src[i], 1);
+    });
+    if (!plan) return rc;
+    return with_pixel(src[0]->bpc, [&](auto px) {
+        typedef decltype(px) pixel;
+        return with_rgb_out<pixel>(dst[0].sample, p, src[0]->bpc, [&](const auto &o) {          // (the type: every item gets the functor of its own depth)
+            typedef std::decay_t<decltype(o)> Out;
+            typedef BatchItem<Out> Item;
+            auto tb = batch_table<Item, 2>(c, n, [&](const int i) { return (int) plan[i].call.tiled; });          // raster items, then twin-only ones
+            if (const int rc = tb.open(0)) return rc;
+            tb.fill([&](const int i, const int t, Item &it) {
+                return rgbx_item_fill<pixel>(it, t, &dst[i], src[i], plan[i].call.planes, plan[i].g, p, plan[i].call.row0, plan[i].call.row1);
+            });
+            return tb.run(1, [](const uint8_t *) { return 0; }, [&](const int t, const Item *const items, const uint32_t *const first, const int n_t, const uint32_t groups) {
+                launch_rgbx_batch<pixel, Out, RESIZE>(c->stream, t, items, first, n_t, groups);
+            });
+        });
+    });
 }
 
 } // namespace

@@ -15,10 +15,12 @@
 //           slots of the context, each guarded by an event recorded behind the launches that read it: the call returns at once, the caller's arrays
 //           are free, and a slot is waited for only when all of them are still in flight.  Slots grow on demand and are freed by dav1d_hip_close
 //           (an outgrown one as well: hipFree waits for the device, capi.h TaskBuf).
+// The host side of all of it — the front of the entry point, the table, the slot, the launches and the events — is surface_batch.h's, which the
+// resized, reduced and colour-managed batches run through as well.
 #include "surface_batch.h"
 
 extern "C" int dav1d_hip_surface_export_rgb_scaled_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst, const Dav1dHipPicture *const *src,
                                                          const Dav1dHipSurfaceRect *crop, const Dav1dHipRgbParams *params, int *bad_item)
 {
-    return export_batch_call<false>(c, n, dst, src, crop, params, bad_item);
+    return export_batch_call<false>(c, n, dst, src, crop, params, 0, bad_item);
 }

@@ -1,7 +1,7 @@
 // What the colour-managed exports share (surface_colour.hip: the whole picture at its own size; surface_colour_reduce.hip: any crop
 // at any size): the handle, the stage behind rgbx_cell as a functor, and the host's choice of cells per wave.
 #pragma once
-#include "surface_common.h"
+#include "surface_call.h"
 
 struct Dav1dHipColour {
     uint8_t *dev;           // lin, then enc (each a multiple of 16 bytes)

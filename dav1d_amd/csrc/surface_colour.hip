@@ -54,14 +54,6 @@ int launch_colour(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, co
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_colour_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
-                         const Dav1dHipRgbParams &p, const Dav1dHipColour *const h, const int row0, const int row1)
-{
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) return launch_colour<pixel, TILED, RgbF32>(c, dst, src, planes, p, h, row0, row1);
-    return launch_colour<pixel, TILED, RgbF16>(c, dst, src, planes, p, h, row0, row1);
-}
-
 bool finite_f32(const float f) { uint32_t x; memcpy(&x, &f, 4); return (x & 0x7f800000u) != 0x7f800000u; }
 
 } // namespace
@@ -111,8 +103,7 @@ extern "C" int dav1d_hip_colour_destroy(Dav1dHipContext *c, Dav1dHipColour *h)
 extern "C" int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipRgbParams *params,
                                                    const Dav1dHipColour *colour, int row0, int row1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     if (!c) return -EINVAL;
     if (const int rc = surface_args_check(dst, src, row0, row1, &call, false, true)) return rc;
@@ -125,13 +116,12 @@ extern "C" int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const Dav
     row0 = call.row0; row1 = call.row1;
     void *const *const planes = call.planes;
     if (row1 <= row0) return 0;
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc;
-    if (src->bpc == 8) rc = call.tiled ? launch_colour_sample<uint8_t, true>(c, dst, src, planes, p, colour, row0, row1) : launch_colour_sample<uint8_t, false>(c, dst, src, planes, p, colour, row0, row1);
-    else rc = call.tiled ? launch_colour_sample<uint16_t, true>(c, dst, src, planes, p, colour, row0, row1) : launch_colour_sample<uint16_t, false>(c, dst, src, planes, p, colour, row0, row1);
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    const CallTimer t(c);
+    return t.done(with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
+        return with_float_out(dst->sample, [&](auto out) {
+            return launch_colour<decltype(px), decltype(state)::value, decltype(out)>(c, dst, src, planes, p, colour, row0, row1);
+        });
+    }));
 }
 
 // ---- dav1d_hip_colour_tables: host arithmetic in double, rounded once to the table's type

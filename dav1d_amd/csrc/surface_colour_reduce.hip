@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void surface_colour_batch_kernel(const ColourI
     const float *const lin = reinterpret_cast<const float *>(lds);
     const ColourFn<Out> fn = { lin, k.has_enc ? reinterpret_cast<const uint16_t *>(lin + k.n_lin) : nullptr, k, out, out.alpha };
     const uint32_t g = blockIdx.x;
-    int lo = 0, hi = n;          // first[lo] <= g < first[hi]
+    int lo = 0, hi = n;          // first[lo] <= g < first[hi] (item_of of surface_batch.h, written out: through the helper this kernel's code comes out another)
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (first[mid] <= g) lo = mid;
@@ -64,81 +64,46 @@ __global__ __launch_bounds__(256) void surface_colour_batch_kernel(const ColourI
 // 0: 4:4:4 and 4:0:0, 1: 4:2:2, 2: 4:2:0 — the instance of the export kernel
 inline int class_of(const ScaleGeom &g) { return g.ss_hor + g.ss_ver; }
 
+// the checked items of a call (n of them; 1: the single call), every one through its Q
 template <typename pixel, typename Out>
 int colour_reduced_run(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src, ReducePlan *const plan,
-                       const Dav1dHipRgbParams &p, const Dav1dHipColour *const h, const size_t q_bytes)
+                       const Dav1dHipRgbParams &p, const Dav1dHipColour *const h)
 {
     typedef typename Out::T T;
+    size_t q_bytes = 0;
+    for (int i = 0; i < n; i++) q_bytes = plan_q(plan[i], src[i], q_bytes);
     if (const int rc = reduce_scratch_take(c, q_bytes)) return rc;
-    int n_cls[3] = { 0, 0, 0 };
-    for (int i = 0; i < n; i++) n_cls[class_of(plan[i].g)]++;
-    // the tables: the items of the export, class by class, a prefix of workgroups per class, the jobs of the reducer (raster, then twin-only)
-    const size_t first_at = (size_t) n * sizeof(ColourItem), jobs_at = round_up(first_at + (size_t) (n + 3) * sizeof(uint32_t), 16);
-    const size_t bytes = jobs_at + (size_t) (3 * n + 2) * sizeof(ReduceJob);
-    Dav1dHipContext::BatchStage *s;
-    if (const int rc = batch_stage_take(c, bytes, &s)) return rc;
-    ColourItem *const items = (ColourItem *) s->host;
-    uint32_t *const first = (uint32_t *) (s->host + first_at);
-    ReduceJob *const jobs = (ReduceJob *) (s->host + jobs_at);
-    const ReduceJobs rj = reduce_jobs_fill<pixel>(c, n, src, plan, p, true, jobs);          // (Q's planes get their addresses here)
-    // ---- the items: every one is read from its Q
-    const int slice0[3] = { 0, n_cls[0], n_cls[0] + n_cls[1] }, first0[3] = { 0, n_cls[0] + 1, n_cls[0] + n_cls[1] + 2 };
-    int fill[3] = { 0, 0, 0 };
-    unsigned total = 0;
-    for (int i = 0; i < n; i++) {
+    // the items of the export, a class per instance of its kernel; behind the table the jobs of the reducer
+    auto tb = batch_table<ColourItem, 3>(c, n, [&](const int i) { return class_of(plan[i].g); });
+    if (const int rc = tb.open((size_t) (3 * n + 2) * sizeof(ReduceJob))) return rc;
+    const ReduceJobs rj = reduce_jobs_fill<pixel>(c, n, src, plan, p, true, (ReduceJob *) tb.extra());          // (Q's planes get their addresses here)
+    const unsigned total = tb.fill([&](const int i, int, ColourItem &it) {
         const ReducePlan &pl = plan[i];
-        const int t = class_of(pl.g);
-        ColourItem &it = items[slice0[t] + fill[t]++];
         void *const planes[3] = { pl.q.p[0].data, pl.q.p[1].data, pl.q.p[2].data };
         it.ax = make_rgbx_args<pixel, false, T>(&dst[i], &pl.q, planes, p, pl.call.row0, pl.call.row1, &it.n_cells);
-        total += it.n_cells;
-    }
+        return it.n_cells;
+    });
     Out out;
     ColourArgs k;
     colour_launch_args(p, h, out, k);
     k.n_cells = total;
     k.C = c->colour_cells ? c->colour_cells : cells_per_wave(total, h->bytes);
-    uint32_t groups[3];
-    for (int t = 0; t < 3; t++) {
-        groups[t] = 0;
-        for (int j = 0; j < n_cls[t]; j++) {
-            first[first0[t] + j] = groups[t];
-            groups[t] += (items[slice0[t] + j].n_cells + 4u * (unsigned) k.C - 1) / (4u * (unsigned) k.C);
-        }
-        first[first0[t] + n_cls[t]] = groups[t];
-    }
-    HIP_TRY(hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, c->stream));
-    const ColourItem *const d_items = (const ColourItem *) s->dev;
-    const uint32_t *const d_first = (const uint32_t *) (s->dev + first_at);
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc = reduce_jobs_launch<pixel>(c, (const ReduceJob *) (s->dev + jobs_at), rj);
-    const dim3 wg(256);
-    hipStream_t st = c->stream;
-    if (groups[0] && !rc) {
-        hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 0, 0, Out>), dim3(groups[0]), wg, h->bytes, st, d_items + slice0[0], d_first + first0[0], n_cls[0], k, out);
-        rc = hip_rc(hipGetLastError());
-    }
-    if (groups[1] && !rc) {
-        hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 0, Out>), dim3(groups[1]), wg, h->bytes, st, d_items + slice0[1], d_first + first0[1], n_cls[1], k, out);
-        rc = hip_rc(hipGetLastError());
-    }
-    if (groups[2] && !rc) {
-        hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 1, Out>), dim3(groups[2]), wg, h->bytes, st, d_items + slice0[2], d_first + first0[2], n_cls[2], k, out);
-        rc = hip_rc(hipGetLastError());
-    }
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    (void) hipEventRecord(s->done, c->stream);
-    s->busy = true;
-    c->last_ms_pending = !rc;
-    return rc;
+    return tb.run(4u * (unsigned) k.C, [&](const uint8_t *const d_jobs) { return reduce_jobs_launch<pixel>(c, (const ReduceJob *) d_jobs, rj); },
+                  [&](const int t, const ColourItem *const items, const uint32_t *const first, const int n_t, const uint32_t groups) {
+                      const dim3 grid(groups), wg(256);
+                      hipStream_t st = c->stream;
+                      if (t == 0) hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 0, 0, Out>), grid, wg, h->bytes, st, items, first, n_t, k, out);
+                      else if (t == 1) hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 0, Out>), grid, wg, h->bytes, st, items, first, n_t, k, out);
+                      else hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 1, Out>), grid, wg, h->bytes, st, items, first, n_t, k, out);
+                  });
 }
 
-template <typename pixel>
 int colour_reduced_run_sample(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src, ReducePlan *const plan,
-                              const Dav1dHipRgbParams &p, const Dav1dHipColour *const h, const size_t q_bytes)
+                              const Dav1dHipRgbParams &p, const Dav1dHipColour *const h)
 {
-    if (dst[0].sample == DAV1D_HIP_SAMPLE_F32) return colour_reduced_run<pixel, RgbF32>(c, n, dst, src, plan, p, h, q_bytes);
-    return colour_reduced_run<pixel, RgbF16>(c, n, dst, src, plan, p, h, q_bytes);
+    return with_pixel(h->bpc, [&](auto px) {
+        return with_float_out(dst[0].sample, [&](auto out) { return colour_reduced_run<decltype(px), decltype(out)>(c, n, dst, src, plan, p, h); });
+    });
 }
 
 // what the single call refuses, in its order (include/dav1d_hip.h)
@@ -160,44 +125,26 @@ int colour_reduced_check(Dav1dHipContext *const c, const Dav1dHipSurface *const 
 extern "C" int dav1d_hip_surface_export_rgb_colour_reduced(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                            const Dav1dHipRgbParams *params, const Dav1dHipColour *colour, int filter, int drow0, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     if (!c) return -EINVAL;
-    ReducePlan *const plan = take_plans(c, 1);
+    ReducePlan *const plan = take_plans<ReducePlan>(c, 1);
     if (!plan) return -ENOMEM;
     if (const int rc = colour_reduced_check(c, dst, src, crop, p, colour, filter, drow0, drow1, plan)) return rc;
     if (plan->call.row1 <= plan->call.row0) return 0;
-    const size_t q_bytes = plan_q(*plan, src, 0);
-    return src->bpc == 8 ? colour_reduced_run_sample<uint8_t>(c, 1, dst, &src, plan, p, colour, q_bytes)
-                         : colour_reduced_run_sample<uint16_t>(c, 1, dst, &src, plan, p, colour, q_bytes);
+    return colour_reduced_run_sample(c, 1, dst, &src, plan, p, colour);
 }
 
 extern "C" int dav1d_hip_surface_export_rgb_colour_reduced_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst, const Dav1dHipPicture *const *src,
                                                                  const Dav1dHipSurfaceRect *crop, const Dav1dHipRgbParams *params, const Dav1dHipColour *colour,
                                                                  int filter, int *bad_item)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
-    if (bad_item) *bad_item = -1;
-    if (!c || n < 0 || n > DAV1D_HIP_SURFACE_BATCH_MAX) return -EINVAL;
-    if (filter != DAV1D_HIP_RESIZE_BILINEAR) return -ENOTSUP;          // the call as a whole
-    if (!colour) return -EINVAL;                                       // ... likewise
-    if (!n) return 0;
-    if (!dst || !src) return -EINVAL;
-    for (int i = 0; i < n; i++)
-        if (!src[i]) { if (bad_item) *bad_item = i; return -EINVAL; }
-    ReducePlan *const plan = take_plans(c, n);
-    if (!plan) return -ENOMEM;
-    size_t q_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        ReducePlan &pl = plan[i];
-        // (an item whose bpc is not the handle's is refused by the single call's rule: stricter than the pixel size of 10.5)
-        int rc = colour_reduced_check(c, &dst[i], src[i], crop ? &crop[i] : nullptr, p, colour, filter, 0, dst[i].h, &pl);
-        // one kernel instance for the batch: format and sample are item 0's
-        if (!rc && (dst[i].format != dst[0].format || dst[i].sample != dst[0].sample)) rc = -EINVAL;
-        if (rc) { if (bad_item) *bad_item = i; return rc; }
-        q_bytes = plan_q(pl, src[i], q_bytes);
-    }
-    return colour->bpc == 8 ? colour_reduced_run_sample<uint8_t>(c, n, dst, src, plan, p, colour, q_bytes)
-                            : colour_reduced_run_sample<uint16_t>(c, n, dst, src, plan, p, colour, q_bytes);
+    const Dav1dHipRgbParams p = rgb_params_of(params);
+    ReducePlan *plan;
+    // the call as a whole: its filter, then its handle.  (An item whose bpc is not the handle's is refused by the single call's rule, which is
+    // stricter than the pixel size of 10.5.)
+    const int whole_rc = filter != DAV1D_HIP_RESIZE_BILINEAR ? -ENOTSUP : !colour ? -EINVAL : 0;
+    const int rc = batch_plans(c, n, dst, src, whole_rc, false, bad_item, &plan, [&](const int i, ReducePlan &pl) {
+        return colour_reduced_check(c, &dst[i], src[i], crop ? &crop[i] : nullptr, p, colour, filter, 0, dst[i].h, &pl);
+    });
+    return plan ? colour_reduced_run_sample(c, n, dst, src, plan, p, colour) : rc;
 }

@@ -3,7 +3,8 @@
 // surface_resize.hip: both with axes that may go up; surface_reduce.hip: both at thumbnail scale; surface_colour.hip and surface_colour_reduce.hip:
 // tensor-ready RGB through a colour stage, at the picture's size and at any size): the 8-sample unit and
 // its loads and stores, the output sample functors, the kernel arguments and how a call is checked and turned into them.  See surface.hip for the
-// layout of a wave (8 rows x 8 units, a 64 x 8 cell of a plane).
+// layout of a wave (8 rows x 8 units, a 64 x 8 cell of a plane), surface_call.h for the path of a call from its check to its launch and
+// surface_batch.h for that of a batch.
 #pragma once
 #include "capi.h"
 #include <string.h>
@@ -731,9 +732,9 @@ struct ScaleGeom {
 };
 
 // the crop and the ratio: what dav1d_hip_surface_export_scaled refuses beyond what the plain export does
-// (`up_ok`: the resizing calls of surface_resize.hip, which serve dst->w > w and dst->h > h)
+// (`up_ok`: the resizing calls of surface_resize.hip, which serve dst->w > w and dst->h > h; `max_ratio`: the reducing calls of surface_reduce.h go past 8:1)
 inline int scale_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, ScaleGeom *const g,
-                            const bool up_ok = false)
+                            const bool up_ok = false, const int max_ratio = 8)
 {
     const int W = src->p[0].w, H = src->p[0].h;
     g->mono = src->layout == DAV1D_HIP_LAYOUT_I400;
@@ -742,7 +743,7 @@ inline int scale_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPict
     g->dw = dst->w; g->dh = dst->h;
     if (g->w <= 0 || g->h <= 0 || g->x0 < 0 || g->y0 < 0 || g->x0 > W - g->w || g->y0 > H - g->h) return -EINVAL;
     if ((g->ss_hor && (g->x0 & 1)) || (g->ss_ver && (g->y0 & 1))) return -EINVAL;
-    if ((!up_ok && (g->dw > g->w || g->dh > g->h)) || g->w > 8LL * g->dw || g->h > 8LL * g->dh) return -ENOTSUP;
+    if ((!up_ok && (g->dw > g->w || g->dh > g->h)) || g->w > (long long) max_ratio * g->dw || g->h > (long long) max_ratio * g->dh) return -ENOTSUP;
     return 0;
 }
 
@@ -763,20 +764,8 @@ ScalePlane make_scale_plane(const Dav1dHipPicture *const src, void *const *const
     return p;
 }
 
-// source luma rows from the top of the picture that destination rows [0, r1) of geometry g read (dav1d_hip_surface_scaled_rows_needed), r1 > 0
-inline int scale_rows_needed(const ScaleGeom &g, const int src_h, const int r1)
-{
-    long long need = g.y0 + ((long long) r1 * g.h + g.dh - 1) / g.dh;
-    if (!g.mono) {
-        const int sh = (g.h + g.ss_ver) >> g.ss_ver, dch = (g.dh + g.ss_ver) >> g.ss_ver, cr1 = r1 >= g.dh ? dch : r1 >> g.ss_ver;
-        const long long cneed = ((long long) (g.y0 >> g.ss_ver) + ((long long) cr1 * sh + dch - 1) / dch) << g.ss_ver;
-        if (cneed > need) need = cneed;
-    }
-    return (int) (need > src_h ? src_h : need);
-}
-
-// the same for the resizing calls (dav1d_hip_surface_rgb_resized_rows_needed): on an axis that goes up, rows [0, r) of a plane read rows
-// [0, min(s, i0(r - 1) + 2)) of its window
+// rows [0, n) of a plane's window of s rows that rows [0, r) of its d outputs read: through S the rows they cover; on an axis that goes up, through R,
+// [0, min(s, i0(r - 1) + 2))
 inline int resize_rows_of(const int r, const int s, const int d)
 {
     if (r <= 0) return 0;
@@ -785,6 +774,7 @@ inline int resize_rows_of(const int r, const int s, const int d)
     const long long rows = (N + D) / D + 1;          // i0 + 2
     return (int) (rows > s ? s : rows);
 }
+// source luma rows from the top of the picture that destination rows [0, r1) of geometry g read, r1 > 0
 inline int resize_rows_needed(const ScaleGeom &g, const int src_h, const int r1)
 {
     long long need = g.y0 + resize_rows_of(r1, g.h, g.dh);
@@ -794,6 +784,15 @@ inline int resize_rows_needed(const ScaleGeom &g, const int src_h, const int r1)
         if (cneed > need) need = cneed;
     }
     return (int) (need > src_h ? src_h : need);
+}
+// What the *_rows_needed call of a sized family answers once its check (`rc`) has filled `call` and `g`: the source rows that destination rows
+// [0, call.row1) read — with `ring` (the tensor-ready families at chroma_pos != 0) those of the chroma row below the band's last, which is made as well
+inline int sized_rows_needed(const int rc, const SurfaceCall &call, const ScaleGeom &g, const bool ring, const Dav1dHipPicture *const src)
+{
+    if (rc) return rc;
+    if (call.row1 <= 0) return 0;
+    const int r = ring && g.ss_ver ? call.row1 + 2 : call.row1;
+    return resize_rows_needed(g, src->p[0].h, r > g.dh ? g.dh : r);
 }
 
 // ---- tensor-ready RGB behind the scaler (surface_rgb_scale.hip has the account of the cell and its ring)
@@ -914,11 +913,11 @@ __device__ __forceinline__ void scale_rgbx_cell(ScaleLds<pixel> &L, const ScaleR
 // the union of what dav1d_hip_surface_export_rgb and dav1d_hip_surface_export_scaled refuse
 inline int rgbx_scaled_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop,
                                   const Dav1dHipRgbParams &p, const int row0, const int row1, SurfaceCall *const call, ScaleGeom *const g,
-                                  const bool up_ok = false)
+                                  const bool up_ok = false, const int max_ratio = 8)
 {
     if (const int rc = surface_args_check(dst, src, row0, row1, call, true, true)) return rc;
     if (const int rc = rgb_params_check(dst, p)) return rc;
-    return scale_geom_check(dst, src, crop, g, up_ok);
+    return scale_geom_check(dst, src, crop, g, up_ok, max_ratio);
 }
 
 // the kernel's arguments for destination luma rows [row0, row1) of a checked call; *n_groups = its workgroups (a cell of Q's chroma planes each)

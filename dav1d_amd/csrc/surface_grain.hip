@@ -13,7 +13,7 @@
 // reads 16 consecutive bytes of one template row, 36 KB of templates serve the whole launch from the caches, and 36 KB of LDS per workgroup
 // would cost more to fill than the workgroup's own pixels.  Which planes get grain is uniform per launch (kernel arguments, not template
 // parameters): a part of a planar surface that gets none runs the plain copy body.
-#include "surface_common.h"
+#include "surface_call.h"
 #include "fg_common.h"
 
 namespace {
@@ -313,23 +313,6 @@ int launch_grain(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, con
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_grain_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
-                        const int row0, const int row1, const GrainArgs &k)
-{
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) {
-        OutF32 o; o.scale = (float) (1.0 / (double) ((1 << src->bpc) - 1));
-        return launch_grain<pixel, TILED, OutF32>(c, dst, src, planes, row0, row1, o, k);
-    }
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst->sample == DAV1D_HIP_SAMPLE_MSB16) {
-            OutMsb16 o; o.shift = 16 - src->bpc;
-            return launch_grain<pixel, TILED, OutMsb16>(c, dst, src, planes, row0, row1, o, k);
-        }
-    }
-    return launch_grain<pixel, TILED, OutNative<pixel>>(c, dst, src, planes, row0, row1, OutNative<pixel>(), k);
-}
-
 // the handle's offsets table of this geometry: a new one (the caller fills it on the context's stream) the first time, kept until the handle goes
 const uint8_t *offsets_of(Dav1dHipContext *const c, const Dav1dHipGrain *const g, const int nbx, const int nby, int *const rc)
 {
@@ -373,19 +356,17 @@ extern "C" int dav1d_hip_surface_export_grain(Dav1dHipContext *c, const Dav1dHip
     for (int i = 0; i < 2; i++) { k.uv_mult[i] = d->uv_mult[i]; k.uv_luma_mult[i] = d->uv_luma_mult[i]; k.uv_offset[i] = d->uv_offset[i] * (1 << bd8); }
     rc = hip_rc(hipStreamWaitEvent(c->stream, grain->ready, 0));
     if (rc) return rc;
-    (void) hipEventRecord(c->ev_t0, c->stream);
+    const CallTimer t(c);          // (behind the wait, in front of the offsets)
     if (grain->offs.size() != n_tables) {
         rc = dav1d_hip_launch_fg_offsets(const_cast<uint8_t *>(offs), d->seed, nby, nbx, c->stream);
         if (rc) { grain->offs.pop_back(); (void) hipFree(const_cast<uint8_t *>(offs)); }        // (nothing was enqueued that reads it)
     }
     void *const *const planes = call.planes;
-    if (!rc) {
-        if (src->bpc == 8) rc = call.tiled ? launch_grain_sample<uint8_t, true>(c, dst, src, planes, call.row0, call.row1, k)
-                                           : launch_grain_sample<uint8_t, false>(c, dst, src, planes, call.row0, call.row1, k);
-        else rc = call.tiled ? launch_grain_sample<uint16_t, true>(c, dst, src, planes, call.row0, call.row1, k)
-                             : launch_grain_sample<uint16_t, false>(c, dst, src, planes, call.row0, call.row1, k);
-    }
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    if (!rc) rc = with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
+        typedef decltype(px) pixel;
+        return with_out<pixel>(dst->sample, src->bpc, [&](const auto &out) {
+            return launch_grain<pixel, decltype(state)::value>(c, dst, src, planes, call.row0, call.row1, out, k);
+        });
+    });
+    return t.done(rc);
 }

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void surface_reduce_kernel(const ReduceJob *co
 {
     __shared__ ReduceLds L;
     const uint32_t g = blockIdx.x;
-    int lo = 0, hi = n;          // jobs[lo].first <= g < jobs[hi].first
+    int lo = 0, hi = n;          // jobs[lo].first <= g < jobs[hi].first (item_of of surface_batch.h over a field: its own loop, which keeps this kernel's code)
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (jobs[mid].first <= g) lo = mid;
@@ -196,29 +196,11 @@ struct ReducePlan {
     size_t q_off[3];
 };
 
-inline size_t round_up(const size_t v, const size_t a) { return (v + a - 1) / a * a; }
-
-// the crop and the ratio: scale_geom_check with these calls' rule
-int reduce_geom_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, ScaleGeom *const g)
-{
-    const int W = src->p[0].w, H = src->p[0].h;
-    g->mono = src->layout == DAV1D_HIP_LAYOUT_I400;
-    g->ss_ver = src->layout == DAV1D_HIP_LAYOUT_I420; g->ss_hor = !g->mono && src->layout != DAV1D_HIP_LAYOUT_I444;
-    g->x0 = crop ? crop->x0 : 0; g->y0 = crop ? crop->y0 : 0; g->w = crop ? crop->w : W; g->h = crop ? crop->h : H;
-    g->dw = dst->w; g->dh = dst->h;
-    if (g->w <= 0 || g->h <= 0 || g->x0 < 0 || g->y0 < 0 || g->x0 > W - g->w || g->y0 > H - g->h) return -EINVAL;
-    if ((g->ss_hor && (g->x0 & 1)) || (g->ss_ver && (g->y0 & 1))) return -EINVAL;
-    if (g->w > (long long) DAV1D_HIP_SURFACE_REDUCE_MAX * g->dw || g->h > (long long) DAV1D_HIP_SURFACE_REDUCE_MAX * g->dh) return -ENOTSUP;
-    return 0;
-}
-
 // what dav1d_hip_surface_export_rgb_resized refuses, in its order, with the ratio rule of these calls
 int reduced_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, const Dav1dHipRgbParams &p,
                        const int filter, const int row0, const int row1, SurfaceCall *const call, ScaleGeom *const g)
 {
-    if (const int rc = surface_args_check(dst, src, row0, row1, call, true, true)) return rc;
-    if (const int rc = rgb_params_check(dst, p)) return rc;
-    if (const int rc = reduce_geom_check(dst, src, crop, g)) return rc;
+    if (const int rc = rgbx_scaled_args_check(dst, src, crop, p, row0, row1, call, g, true, DAV1D_HIP_SURFACE_REDUCE_MAX)) return rc;
     return filter == DAV1D_HIP_RESIZE_BILINEAR ? 0 : -ENOTSUP;
 }
 
@@ -250,17 +232,6 @@ void job_cell(ReduceJob &j)
     const int rows = j.j1 - j.j0;
     const bool large = (long long) p.sw * p.sh >= 1 << 20;
     p.oh = !large || (long long) j.n_cx * ((rows + 3) / 4) >= 512 ? 4 : (long long) j.n_cx * ((rows + 1) / 2) >= 512 ? 2 : 1;
-}
-
-// the plans of a call live in the context's batch_plan
-ReducePlan *take_plans(Dav1dHipContext *const c, const int n)
-{
-    try {
-        if (c->batch_plan.size() < (size_t) n * sizeof(ReducePlan) + alignof(ReducePlan)) c->batch_plan.resize((size_t) n * sizeof(ReducePlan) + alignof(ReducePlan));
-    } catch (...) {
-        return nullptr;
-    }
-    return (ReducePlan *) round_up((size_t) (uintptr_t) c->batch_plan.data(), alignof(ReducePlan));
 }
 
 // the context's scratch holds q_bytes: grown on demand, an outgrown one is retired, not freed (launches in flight may read it)

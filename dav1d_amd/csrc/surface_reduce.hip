@@ -22,99 +22,50 @@
 
 namespace {
 
-// the export of the batch: surface_batch.h's kernel under a name of this unit
-template <typename pixel, bool TILED, typename Out>
-__global__ __launch_bounds__(256, sizeof(pixel) == 1 ? 5 : 4) void surface_reduced_rgbx_kernel(const BatchItem<Out> *const __restrict__ items, const uint32_t *const __restrict__ first,
-                                                                                                const int n)
-{
-    __shared__ ScaleLds<pixel> L;
-    const uint32_t g = blockIdx.x;
-    int lo = 0, hi = n;          // first[lo] <= g < first[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    const BatchItem<Out> &it = items[lo];
-    ScaleRgbxArgs a = it.a;
-    for (int pl = 0; pl < 3; pl++) { a.pl[pl].s = in_device_memory(a.pl[pl].s); a.c.d[pl] = in_device_memory(a.c.d[pl]); }
-    scale_rgbx_cell<pixel, TILED, Out, true>(L, a, (int) (g - first[lo]), it.out);
-}
-
 // ---- the host side
 
+// the checked items of a call (n of them; 1: the single call), those past 8:1 through their Q
 template <typename pixel, typename Out>
 int reduced_run(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src, ReducePlan *const plan,
-                const Dav1dHipRgbParams &p, const size_t q_bytes)
+                const Dav1dHipRgbParams &p)
 {
     typedef BatchItem<Out> Item;
-    int n_red = 0, n_exp[2] = { 0, 0 };
-    for (int i = 0; i < n; i++) { n_red += plan[i].reduce; n_exp[!plan[i].reduce && plan[i].call.tiled]++; }
-    if (const int rc = reduce_scratch_take(c, q_bytes)) return rc;
-    // the tables: the items of the export (raster, then twin-only), their two prefixes, the jobs of the reducer (raster, then twin-only)
-    const size_t first_at = (size_t) n * sizeof(Item), jobs_at = round_up(first_at + (size_t) (n + 2) * sizeof(uint32_t), 16);
-    const size_t bytes = jobs_at + (size_t) (3 * n_red + 2) * sizeof(ReduceJob);
-    Dav1dHipContext::BatchStage *s;
-    if (const int rc = batch_stage_take(c, bytes, &s)) return rc;
-    Item *const items = (Item *) s->host;
-    uint32_t *const first = (uint32_t *) (s->host + first_at);
-    ReduceJob *const jobs = (ReduceJob *) (s->host + jobs_at);
-    const ReduceJobs rj = reduce_jobs_fill<pixel>(c, n, src, plan, p, false, jobs);
-    // ---- the items of the export: a reduced item is read from its Q, in raster order (counted with the raster items above)
-    const int slice0[2] = { 0, n_exp[0] }, first0[2] = { 0, n_exp[0] + 1 };
-    int fill[2] = { 0, 0 };
-    uint32_t groups[2] = { 0, 0 };
+    int n_red = 0;
+    size_t q_bytes = 0;
     for (int i = 0; i < n; i++) {
+        ReducePlan &pl = plan[i];
+        pl.reduce = pl.g.w > 8LL * pl.g.dw || pl.g.h > 8LL * pl.g.dh;
+        if (pl.reduce) { q_bytes = plan_q(pl, src[i], q_bytes); n_red++; }
+    }
+    if (const int rc = reduce_scratch_take(c, q_bytes)) return rc;
+    // the items of the export: raster ones — a reduced item is read from its Q, whatever its source — then twin-only ones; behind the table the jobs
+    // of the reducer
+    auto tb = batch_table<Item, 2>(c, n, [&](const int i) { return (int) (!plan[i].reduce && plan[i].call.tiled); });
+    if (const int rc = tb.open((size_t) (3 * n_red + 2) * sizeof(ReduceJob))) return rc;
+    const ReduceJobs rj = reduce_jobs_fill<pixel>(c, n, src, plan, p, false, (ReduceJob *) tb.extra());
+    tb.fill([&](const int i, const int t, Item &it) {
         const ReducePlan &pl = plan[i];
-        const int t = !pl.reduce && pl.call.tiled, k = fill[t]++;
-        Item &it = items[slice0[t] + k];
-        unsigned ng;
-        if (pl.reduce) {
-            ScaleGeom gq = pl.g;
-            gq.x0 = gq.y0 = 0; gq.w = gq.dw; gq.h = gq.dh;
-            void *const planes[3] = { pl.q.p[0].data, pl.q.p[1].data, pl.q.p[2].data };
-            it.a = make_scale_rgbx_args<pixel, false, typename Out::T>(&dst[i], &pl.q, planes, gq, p, pl.call.row0, pl.call.row1, &ng);
-        } else {
-            it.a = t ? make_scale_rgbx_args<pixel, true, typename Out::T>(&dst[i], src[i], pl.call.planes, pl.g, p, pl.call.row0, pl.call.row1, &ng)
-                     : make_scale_rgbx_args<pixel, false, typename Out::T>(&dst[i], src[i], pl.call.planes, pl.g, p, pl.call.row0, pl.call.row1, &ng);
-        }
-        it.out = Out();
-        set_out(it.out, p, src[i]->bpc);
-        first[first0[t] + k] = groups[t];
-        groups[t] += ng;
-    }
-    for (int t = 0; t < 2; t++) first[first0[t] + n_exp[t]] = groups[t];
-    HIP_TRY(hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, c->stream));
-    const Item *const d_items = (const Item *) s->dev;
-    const uint32_t *const d_first = (const uint32_t *) (s->dev + first_at);
-    const ReduceJob *const d_jobs = (const ReduceJob *) (s->dev + jobs_at);
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc = reduce_jobs_launch<pixel>(c, d_jobs, rj);
-    if (groups[0] && !rc) {
-        hipLaunchKernelGGL((surface_reduced_rgbx_kernel<pixel, false, Out>), dim3(groups[0]), dim3(256), 0, c->stream, d_items, d_first, n_exp[0]);
-        rc = hip_rc(hipGetLastError());
-    }
-    if (groups[1] && !rc) {
-        hipLaunchKernelGGL((surface_reduced_rgbx_kernel<pixel, true, Out>), dim3(groups[1]), dim3(256), 0, c->stream, d_items + slice0[1], d_first + first0[1], n_exp[1]);
-        rc = hip_rc(hipGetLastError());
-    }
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    (void) hipEventRecord(s->done, c->stream);
-    s->busy = true;
-    c->last_ms_pending = !rc;
-    return rc;
+        if (!pl.reduce) return rgbx_item_fill<pixel>(it, t, &dst[i], src[i], pl.call.planes, pl.g, p, pl.call.row0, pl.call.row1);
+        ScaleGeom gq = pl.g;
+        gq.x0 = gq.y0 = 0; gq.w = gq.dw; gq.h = gq.dh;
+        void *const planes[3] = { pl.q.p[0].data, pl.q.p[1].data, pl.q.p[2].data };
+        return rgbx_item_fill<pixel>(it, false, &dst[i], &pl.q, planes, gq, p, pl.call.row0, pl.call.row1);
+    });
+    return tb.run(1, [&](const uint8_t *const d_jobs) { return reduce_jobs_launch<pixel>(c, (const ReduceJob *) d_jobs, rj); },
+                  [&](const int t, const Item *const items, const uint32_t *const first, const int n_t, const uint32_t groups) {
+                      launch_rgbx_batch<pixel, Out, true>(c->stream, t, items, first, n_t, groups);
+                  });
 }
 
-template <typename pixel>
 int reduced_run_sample(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src, ReducePlan *const plan,
-                       const Dav1dHipRgbParams &p, const size_t q_bytes)
+                       const Dav1dHipRgbParams &p)
 {
-    if (dst[0].sample == DAV1D_HIP_SAMPLE_F32) return reduced_run<pixel, RgbF32>(c, n, dst, src, plan, p, q_bytes);
-    if (dst[0].sample == DAV1D_HIP_SAMPLE_F16) return reduced_run<pixel, RgbF16>(c, n, dst, src, plan, p, q_bytes);
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst[0].sample == DAV1D_HIP_SAMPLE_MSB16) return reduced_run<pixel, RgbInt<OutMsb16>>(c, n, dst, src, plan, p, q_bytes);
-    }
-    return reduced_run<pixel, RgbInt<OutNative<pixel>>>(c, n, dst, src, plan, p, q_bytes);
+    return with_pixel(src[0]->bpc, [&](auto px) {
+        typedef decltype(px) pixel;
+        return with_rgb_out<pixel>(dst[0].sample, p, src[0]->bpc, [&](const auto &o) {          // (the type: every item gets the functor of its own depth)
+            return reduced_run<pixel, std::decay_t<decltype(o)>>(c, n, dst, src, plan, p);
+        });
+    });
 }
 
 } // namespace
@@ -122,57 +73,33 @@ int reduced_run_sample(Dav1dHipContext *const c, const int n, const Dav1dHipSurf
 extern "C" int dav1d_hip_surface_export_rgb_reduced(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                     const Dav1dHipRgbParams *params, int filter, int drow0, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     if (!c) return -EINVAL;
-    ReducePlan *const plan = take_plans(c, 1);
+    ReducePlan *const plan = take_plans<ReducePlan>(c, 1);
     if (!plan) return -ENOMEM;
     if (const int rc = reduced_args_check(dst, src, crop, p, filter, drow0, drow1, &plan->call, &plan->g)) return rc;
     if (const int rc = pictures_on_device(c, src, 1)) return rc;
     if (plan->call.row1 <= plan->call.row0) return 0;
-    plan->reduce = plan->g.w > 8LL * plan->g.dw || plan->g.h > 8LL * plan->g.dh;
-    const size_t q_bytes = plan->reduce ? plan_q(*plan, src, 0) : 0;
-    return src->bpc == 8 ? reduced_run_sample<uint8_t>(c, 1, dst, &src, plan, p, q_bytes) : reduced_run_sample<uint16_t>(c, 1, dst, &src, plan, p, q_bytes);
+    return reduced_run_sample(c, 1, dst, &src, plan, p);
 }
 
 extern "C" int dav1d_hip_surface_rgb_reduced_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                          const Dav1dHipRgbParams *params, int filter, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     ScaleGeom g;
-    if (const int rc = reduced_args_check(dst, src, crop, p, filter, 0, drow1, &call, &g)) return rc;
-    if (call.row1 <= 0) return 0;
-    // the ring: the chroma row below the band's last is made as well
-    const int r = g.ss_ver && p.chroma_pos ? call.row1 + 2 : call.row1;
-    return resize_rows_needed(g, src->p[0].h, r > g.dh ? g.dh : r);
+    return sized_rows_needed(reduced_args_check(dst, src, crop, p, filter, 0, drow1, &call, &g), call, g, p.chroma_pos != 0, src);
 }
 
 extern "C" int dav1d_hip_surface_export_rgb_reduced_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst, const Dav1dHipPicture *const *src,
                                                           const Dav1dHipSurfaceRect *crop, const Dav1dHipRgbParams *params, int filter, int *bad_item)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
-    if (bad_item) *bad_item = -1;
-    if (!c || n < 0 || n > DAV1D_HIP_SURFACE_BATCH_MAX) return -EINVAL;
-    if (filter != DAV1D_HIP_RESIZE_BILINEAR) return -ENOTSUP;          // the call as a whole
-    if (!n) return 0;
-    if (!dst || !src) return -EINVAL;
-    for (int i = 0; i < n; i++)
-        if (!src[i]) { if (bad_item) *bad_item = i; return -EINVAL; }
-    ReducePlan *const plan = take_plans(c, n);
-    if (!plan) return -ENOMEM;
-    size_t q_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        ReducePlan &pl = plan[i];
-        int rc = reduced_args_check(&dst[i], src[i], crop ? &crop[i] : nullptr, p, filter, 0, dst[i].h, &pl.call, &pl.g);
-        if (!rc) rc = pictures_on_device(c, src[i], 1);
-        // one kernel instance for the batch: format, sample and pixel size are item 0's
-        if (!rc && (dst[i].format != dst[0].format || dst[i].sample != dst[0].sample || (src[i]->bpc == 8) != (src[0]->bpc == 8))) rc = -EINVAL;
-        if (rc) { if (bad_item) *bad_item = i; return rc; }
-        pl.reduce = pl.g.w > 8LL * pl.g.dw || pl.g.h > 8LL * pl.g.dh;
-        if (pl.reduce) q_bytes = plan_q(pl, src[i], q_bytes);
-    }
-    return src[0]->bpc == 8 ? reduced_run_sample<uint8_t>(c, n, dst, src, plan, p, q_bytes) : reduced_run_sample<uint16_t>(c, n, dst, src, plan, p, q_bytes);
+    const Dav1dHipRgbParams p = rgb_params_of(params);
+    ReducePlan *plan;
+    const int rc = batch_plans(c, n, dst, src, filter == DAV1D_HIP_RESIZE_BILINEAR ? 0 : -ENOTSUP, true, bad_item, &plan, [&](const int i, ReducePlan &pl) {
+        const int rc = reduced_args_check(&dst[i], src[i], crop ? &crop[i] : nullptr, p, filter, 0, dst[i].h, &pl.call, &pl.g);
+        return rc ? rc : pictures_on_device(c, src[i], 1);
+    });
+    return plan ? reduced_run_sample(c, n, dst, src, plan, p) : rc;
 }

@@ -37,28 +37,6 @@ int launch_rgbx_resized(Dav1dHipContext *const c, const Dav1dHipSurface *const d
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_rgbx_resized_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
-                               const ScaleGeom &g, const Dav1dHipRgbParams &p, const int row0, const int row1)
-{
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) {
-        RgbF32 o; set_out(o, p, src->bpc);
-        return launch_rgbx_resized<pixel, TILED, RgbF32>(c, dst, src, planes, g, p, row0, row1, o);
-    }
-    if (dst->sample == DAV1D_HIP_SAMPLE_F16) {
-        RgbF16 o; set_out(o, p, src->bpc);
-        return launch_rgbx_resized<pixel, TILED, RgbF16>(c, dst, src, planes, g, p, row0, row1, o);
-    }
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst->sample == DAV1D_HIP_SAMPLE_MSB16) {
-            RgbInt<OutMsb16> o; set_out(o, p, src->bpc);
-            return launch_rgbx_resized<pixel, TILED, RgbInt<OutMsb16>>(c, dst, src, planes, g, p, row0, row1, o);
-        }
-    }
-    RgbInt<OutNative<pixel>> o; set_out(o, p, src->bpc);
-    return launch_rgbx_resized<pixel, TILED, RgbInt<OutNative<pixel>>>(c, dst, src, planes, g, p, row0, row1, o);
-}
-
 // what dav1d_hip_surface_export_rgb_scaled refuses, in its order, less the size rule; then the filter
 int resized_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipSurfaceRect *const crop, const Dav1dHipRgbParams &p,
                        const int filter, const int row0, const int row1, SurfaceCall *const call, ScaleGeom *const g)
@@ -72,8 +50,7 @@ int resized_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *
 extern "C" int dav1d_hip_surface_export_rgb_resized(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                     const Dav1dHipRgbParams *params, int filter, int drow0, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     ScaleGeom g;
     if (!c) return -EINVAL;
@@ -82,34 +59,26 @@ extern "C" int dav1d_hip_surface_export_rgb_resized(Dav1dHipContext *c, const Da
     const int row0 = call.row0, row1 = call.row1;
     if (row1 <= row0) return 0;
     void *const *const planes = call.planes;
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc;
-    if (src->bpc == 8) rc = call.tiled ? launch_rgbx_resized_sample<uint8_t, true>(c, dst, src, planes, g, p, row0, row1) : launch_rgbx_resized_sample<uint8_t, false>(c, dst, src, planes, g, p, row0, row1);
-    else rc = call.tiled ? launch_rgbx_resized_sample<uint16_t, true>(c, dst, src, planes, g, p, row0, row1) : launch_rgbx_resized_sample<uint16_t, false>(c, dst, src, planes, g, p, row0, row1);
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    const CallTimer t(c);
+    return t.done(with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
+        typedef decltype(px) pixel;
+        return with_rgb_out<pixel>(dst->sample, p, src->bpc, [&](const auto &out) {
+            return launch_rgbx_resized<pixel, decltype(state)::value>(c, dst, src, planes, g, p, row0, row1, out);
+        });
+    }));
 }
 
 extern "C" int dav1d_hip_surface_rgb_resized_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                          const Dav1dHipRgbParams *params, int filter, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     ScaleGeom g;
-    if (const int rc = resized_args_check(dst, src, crop, p, filter, 0, drow1, &call, &g)) return rc;
-    if (call.row1 <= 0) return 0;
-    // the ring: the chroma row below the band's last is resized as well
-    const int r = g.ss_ver && p.chroma_pos ? call.row1 + 2 : call.row1;
-    return resize_rows_needed(g, src->p[0].h, r > g.dh ? g.dh : r);
+    return sized_rows_needed(resized_args_check(dst, src, crop, p, filter, 0, drow1, &call, &g), call, g, p.chroma_pos != 0, src);
 }
 
 extern "C" int dav1d_hip_surface_export_rgb_resized_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst, const Dav1dHipPicture *const *src,
                                                           const Dav1dHipSurfaceRect *crop, const Dav1dHipRgbParams *params, int filter, int *bad_item)
 {
-    if (bad_item) *bad_item = -1;
-    if (!c || n < 0 || n > DAV1D_HIP_SURFACE_BATCH_MAX) return -EINVAL;
-    if (filter != DAV1D_HIP_RESIZE_BILINEAR) return -ENOTSUP;          // the call as a whole
-    return export_batch_call<true>(c, n, dst, src, crop, params, bad_item);
+    return export_batch_call<true>(c, n, dst, src, crop, params, filter == DAV1D_HIP_RESIZE_BILINEAR ? 0 : -ENOTSUP, bad_item);
 }

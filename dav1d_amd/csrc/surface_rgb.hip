@@ -15,7 +15,7 @@
 // both halves.  The vertical taps (sum 4) are applied first, without rounding: P[i][m] for luma row i of the lane and chroma column m = 0 .. 8
 // (8: the neighbour to the right); the horizontal taps (sum 2) and the single rounding (+ 4) >> 3 follow per luma sample.  Columns right of the
 // plane repeat its last one (the clamp of the definition), rows above / below it repeat the first / last.
-#include "surface_common.h"
+#include "surface_call.h"
 
 namespace {
 
@@ -49,29 +49,6 @@ int launch_rgbx(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, cons
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_rgbx_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
-                       const Dav1dHipRgbParams &p, const int row0, const int row1)
-{
-    const int max = (1 << src->bpc) - 1;
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) {
-        RgbF32 o; set_float(o, p, src->bpc); o.alpha = 1.0f;
-        return launch_rgbx<pixel, TILED, RgbF32>(c, dst, src, planes, p, row0, row1, o);
-    }
-    if (dst->sample == DAV1D_HIP_SAMPLE_F16) {
-        RgbF16 o; set_float(o, p, src->bpc); o.alpha = 0x3c00;
-        return launch_rgbx<pixel, TILED, RgbF16>(c, dst, src, planes, p, row0, row1, o);
-    }
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst->sample == DAV1D_HIP_SAMPLE_MSB16) {
-            RgbInt<OutMsb16> o; o.b.shift = 16 - src->bpc; o.alpha = (uint16_t) (max << o.b.shift);
-            return launch_rgbx<pixel, TILED, RgbInt<OutMsb16>>(c, dst, src, planes, p, row0, row1, o);
-        }
-    }
-    RgbInt<OutNative<pixel>> o; o.alpha = (pixel) max;
-    return launch_rgbx<pixel, TILED, RgbInt<OutNative<pixel>>>(c, dst, src, planes, p, row0, row1, o);
-}
-
 // what the call refuses beyond the export's own rules
 int rgbx_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, const Dav1dHipRgbParams &p, const int row0, const int row1,
                     SurfaceCall *const call)
@@ -86,8 +63,7 @@ int rgbx_args_check(const Dav1dHipSurface *const dst, const Dav1dHipPicture *con
 extern "C" int dav1d_hip_surface_export_rgb(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipRgbParams *params,
                                             int row0, int row1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     if (!c) return -EINVAL;
     if (const int rc = rgbx_args_check(dst, src, p, row0, row1, &call)) return rc;
@@ -95,19 +71,18 @@ extern "C" int dav1d_hip_surface_export_rgb(Dav1dHipContext *c, const Dav1dHipSu
     row0 = call.row0; row1 = call.row1;
     void *const *const planes = call.planes;
     if (row1 <= row0) return 0;
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc;
-    if (src->bpc == 8) rc = call.tiled ? launch_rgbx_sample<uint8_t, true>(c, dst, src, planes, p, row0, row1) : launch_rgbx_sample<uint8_t, false>(c, dst, src, planes, p, row0, row1);
-    else rc = call.tiled ? launch_rgbx_sample<uint16_t, true>(c, dst, src, planes, p, row0, row1) : launch_rgbx_sample<uint16_t, false>(c, dst, src, planes, p, row0, row1);
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    const CallTimer t(c);
+    return t.done(with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
+        typedef decltype(px) pixel;
+        return with_rgb_out<pixel>(dst->sample, p, src->bpc, [&](const auto &out) {
+            return launch_rgbx<pixel, decltype(state)::value>(c, dst, src, planes, p, row0, row1, out);
+        });
+    }));
 }
 
 extern "C" int dav1d_hip_surface_rgb_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipRgbParams *params, int row1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     if (const int rc = rgbx_args_check(dst, src, p, 0, row1, &call)) return rc;
     const int h = src->p[0].h, r1 = call.row1;

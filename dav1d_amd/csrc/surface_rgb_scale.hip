@@ -18,7 +18,7 @@
 //
 // The kernel's body is scale_rgbx_cell of surface_common.h, and the host side that checks a call and fills ScaleRgbxArgs is there too: surface_batch.hip
 // runs the same body from a table of such calls.
-#include "surface_common.h"
+#include "surface_call.h"
 
 namespace {
 
@@ -41,35 +41,12 @@ int launch_rgbx_scaled(Dav1dHipContext *const c, const Dav1dHipSurface *const ds
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_rgbx_scaled_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
-                              const ScaleGeom &g, const Dav1dHipRgbParams &p, const int row0, const int row1)
-{
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) {
-        RgbF32 o; set_out(o, p, src->bpc);
-        return launch_rgbx_scaled<pixel, TILED, RgbF32>(c, dst, src, planes, g, p, row0, row1, o);
-    }
-    if (dst->sample == DAV1D_HIP_SAMPLE_F16) {
-        RgbF16 o; set_out(o, p, src->bpc);
-        return launch_rgbx_scaled<pixel, TILED, RgbF16>(c, dst, src, planes, g, p, row0, row1, o);
-    }
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst->sample == DAV1D_HIP_SAMPLE_MSB16) {
-            RgbInt<OutMsb16> o; set_out(o, p, src->bpc);
-            return launch_rgbx_scaled<pixel, TILED, RgbInt<OutMsb16>>(c, dst, src, planes, g, p, row0, row1, o);
-        }
-    }
-    RgbInt<OutNative<pixel>> o; set_out(o, p, src->bpc);
-    return launch_rgbx_scaled<pixel, TILED, RgbInt<OutNative<pixel>>>(c, dst, src, planes, g, p, row0, row1, o);
-}
-
 } // namespace
 
 extern "C" int dav1d_hip_surface_export_rgb_scaled(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                    const Dav1dHipRgbParams *params, int drow0, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     ScaleGeom g;
     if (!c) return -EINVAL;
@@ -78,25 +55,20 @@ extern "C" int dav1d_hip_surface_export_rgb_scaled(Dav1dHipContext *c, const Dav
     const int row0 = call.row0, row1 = call.row1;
     if (row1 <= row0) return 0;
     void *const *const planes = call.planes;
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc;
-    if (src->bpc == 8) rc = call.tiled ? launch_rgbx_scaled_sample<uint8_t, true>(c, dst, src, planes, g, p, row0, row1) : launch_rgbx_scaled_sample<uint8_t, false>(c, dst, src, planes, g, p, row0, row1);
-    else rc = call.tiled ? launch_rgbx_scaled_sample<uint16_t, true>(c, dst, src, planes, g, p, row0, row1) : launch_rgbx_scaled_sample<uint16_t, false>(c, dst, src, planes, g, p, row0, row1);
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    const CallTimer t(c);
+    return t.done(with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
+        typedef decltype(px) pixel;
+        return with_rgb_out<pixel>(dst->sample, p, src->bpc, [&](const auto &out) {
+            return launch_rgbx_scaled<pixel, decltype(state)::value>(c, dst, src, planes, g, p, row0, row1, out);
+        });
+    }));
 }
 
 extern "C" int dav1d_hip_surface_rgb_scaled_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                         const Dav1dHipRgbParams *params, int drow1)
 {
-    Dav1dHipRgbParams p = Dav1dHipRgbParams();
-    if (params) p = *params;
+    const Dav1dHipRgbParams p = rgb_params_of(params);
     SurfaceCall call;
     ScaleGeom g;
-    if (const int rc = rgbx_scaled_args_check(dst, src, crop, p, 0, drow1, &call, &g)) return rc;
-    if (call.row1 <= 0) return 0;
-    // the ring: the chroma row below the band's last is scaled as well
-    const int r = g.ss_ver && p.chroma_pos ? call.row1 + 2 : call.row1;
-    return scale_rows_needed(g, src->p[0].h, r > g.dh ? g.dh : r);
+    return sized_rows_needed(rgbx_scaled_args_check(dst, src, crop, p, 0, drow1, &call, &g), call, g, p.chroma_pos != 0, src);
 }

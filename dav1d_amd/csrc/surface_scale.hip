@@ -12,7 +12,7 @@
 //     across    out[j][o] = (sum wx * t + 2^19) >> 20, v_mad_u32_u24: both factors below 2^24, the sum below 2^32  (LDS)
 //     store     a lane leaves 8 adjacent samples through the export's functors and store_run
 // Semi-planar chroma and RGB run the scaler two or three times in the workgroup (U, V, then Y cell by cell above them) and combine from LDS.
-#include "surface_common.h"
+#include "surface_call.h"
 
 namespace {
 
@@ -163,23 +163,6 @@ int launch_scaled(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, co
     return hip_rc(hipGetLastError());
 }
 
-template <typename pixel, bool TILED>
-int launch_scaled_sample(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
-                         const ScaleGeom &g, const int row0, const int row1)
-{
-    if (dst->sample == DAV1D_HIP_SAMPLE_F32) {
-        OutF32 o; o.scale = (float) (1.0 / (double) ((1 << src->bpc) - 1));
-        return launch_scaled<pixel, TILED, OutF32>(c, dst, src, planes, g, row0, row1, o);
-    }
-    if constexpr (sizeof(pixel) == 2) {
-        if (dst->sample == DAV1D_HIP_SAMPLE_MSB16) {
-            OutMsb16 o; o.shift = 16 - src->bpc;
-            return launch_scaled<pixel, TILED, OutMsb16>(c, dst, src, planes, g, row0, row1, o);
-        }
-    }
-    return launch_scaled<pixel, TILED, OutNative<pixel>>(c, dst, src, planes, g, row0, row1, OutNative<pixel>());
-}
-
 } // namespace
 
 extern "C" int dav1d_hip_surface_export_scaled(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
@@ -192,13 +175,13 @@ extern "C" int dav1d_hip_surface_export_scaled(Dav1dHipContext *c, const Dav1dHi
     const int row0 = call.row0, row1 = call.row1;
     if (row1 <= row0) return 0;
     void *const *const planes = call.planes;
-    (void) hipEventRecord(c->ev_t0, c->stream);
-    int rc;
-    if (src->bpc == 8) rc = call.tiled ? launch_scaled_sample<uint8_t, true>(c, dst, src, planes, g, row0, row1) : launch_scaled_sample<uint8_t, false>(c, dst, src, planes, g, row0, row1);
-    else rc = call.tiled ? launch_scaled_sample<uint16_t, true>(c, dst, src, planes, g, row0, row1) : launch_scaled_sample<uint16_t, false>(c, dst, src, planes, g, row0, row1);
-    (void) hipEventRecord(c->ev_t1, c->stream);
-    c->last_ms_pending = !rc;
-    return rc;
+    const CallTimer t(c);
+    return t.done(with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
+        typedef decltype(px) pixel;
+        return with_out<pixel>(dst->sample, src->bpc, [&](const auto &out) {
+            return launch_scaled<pixel, decltype(state)::value>(c, dst, src, planes, g, row0, row1, out);
+        });
+    }));
 }
 
 extern "C" int dav1d_hip_surface_scaled_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop, int drow1)
@@ -206,8 +189,5 @@ extern "C" int dav1d_hip_surface_scaled_rows_needed(const Dav1dHipSurface *dst, 
     SurfaceCall call;
     if (const int rc = surface_args_check(dst, src, 0, drow1, &call, true)) return rc;
     ScaleGeom g;
-    if (const int rc = scale_geom_check(dst, src, crop, &g)) return rc;
-    const int r1 = call.row1;
-    if (r1 <= 0) return 0;
-    return scale_rows_needed(g, src->p[0].h, r1);
+    return sized_rows_needed(scale_geom_check(dst, src, crop, &g), call, g, false, src);
 }

@@ -49,5 +49,5 @@ if __name__ == "__main__":
     flags = [a for a in sys.argv[1:] if a.startswith("-")]
     for src in (a for a in sys.argv[1:] if not a.startswith("-")):
         for k in report(src, flags):
-            print("%-12s vgpr %3d agpr %3d scratch %4d lds %6d occ %2d  %s" % (src, k.get("vgpr", -1), k.get("agpr", -1), k.get("scratch", -1),
-                                                                               k["lds"], k.get("occ", -1), k["name"][:100]))
+            print("%-12s vgpr %3d agpr %3d sgpr %3d scratch %4d lds %6d occ %2d  %s" % (src, k.get("vgpr", -1), k.get("agpr", -1), k.get("sgpr", -1),
+                                                                                        k.get("scratch", -1), k["lds"], k.get("occ", -1), k["name"][:100]))
