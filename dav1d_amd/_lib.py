@@ -109,6 +109,8 @@ SYMBOLS = [
     "dav1d_hip_surface_export_rgb_resized", "dav1d_hip_surface_rgb_resized_rows_needed", "dav1d_hip_surface_export_rgb_resized_batch",
     "dav1d_hip_surface_export_rgb_reduced", "dav1d_hip_surface_rgb_reduced_rows_needed", "dav1d_hip_surface_export_rgb_reduced_batch",
     "dav1d_hip_surface_export_rgb_colour_reduced", "dav1d_hip_surface_export_rgb_colour_reduced_batch",
+    "dav1d_hip_surface_export_rgb_linear_reduced", "dav1d_hip_surface_export_rgb_linear_reduced_batch", "dav1d_hip_surface_rgb_linear_rows_needed",
+    "dav1d_hip_colour_light_table",
 ]
 
 
@@ -328,6 +330,10 @@ def load(path=None):
         "dav1d_hip_surface_rgb_reduced_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
         "dav1d_hip_surface_export_rgb_colour_reduced": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), vp, i, i, i]),
         "dav1d_hip_surface_export_rgb_colour_reduced_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), vp, i, P(i)]),
+        "dav1d_hip_surface_export_rgb_linear_reduced": (i, [vp, P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), vp, i, i, i]),
+        "dav1d_hip_surface_export_rgb_linear_reduced_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), vp, i, P(i)]),
+        "dav1d_hip_surface_rgb_linear_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
+        "dav1d_hip_colour_light_table": (i, [vp, vp, vp, P(i)]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

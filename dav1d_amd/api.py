@@ -240,6 +240,22 @@ class DevicePicture:
         _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_colour_reduced(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), colour,
                                                                       int(filter), row0, row1), "surface_export_rgb_colour_reduced")
 
+    def export_rgb_linear_reduced(self, surface, colour, crop=None, chroma_pos=0, scale=None, bias=None, row0=0, row1=1 << 30, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_linear_reduced: export_rgb_colour_reduced that scales in LINEAR LIGHT — the rectangle `crop` is converted to
+        RGB and linearised at its own size (sited chroma at source resolution), the light is averaged with the weights of export_rgb_reduced, and the
+        matrix, enc and normalisation of `colour` follow.  Float surfaces only; a handle whose lin has a negative entry is refused.  Asynchronous
+        like export."""
+        p = self._rgb_params(chroma_pos, scale, bias)
+        _chk(self.ctx.lib.dav1d_hip_surface_export_rgb_linear_reduced(self.ctx.h, C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), colour,
+                                                                      int(filter), row0, row1), "surface_export_rgb_linear_reduced")
+
+    def rgb_linear_rows_needed(self, surface, crop, chroma_pos, row1, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_rgb_linear_rows_needed: the source luma rows, from the top, that destination rows [0, row1) of export_rgb_linear_reduced read"""
+        p = self._rgb_params(chroma_pos, None, None)
+        n = self.ctx.lib.dav1d_hip_surface_rgb_linear_rows_needed(C.byref(surface.desc), C.byref(self.pic), self._rect(crop), C.byref(p), int(filter), row1)
+        _chk(min(n, 0), "surface_rgb_linear_rows_needed")
+        return n
+
     @classmethod
     def view(cls, ctx, pic, w, h, layout, bpc):
         """A non-owning wrapper around a Picture descriptor (e.g. the frame-owned output of FrameInFlight.end())."""
@@ -479,12 +495,13 @@ def _colour_sample(tensor):
     return SAMPLE_F32 if tensor.dtype == torch.float32 else SAMPLE_F16
 
 
-def export_colour_to_tensor(pic, tensor, colour, crop=None, matrix=1, full_range=0, chroma_pos=None, scale=None, bias=None):
+def export_colour_to_tensor(pic, tensor, colour, crop=None, matrix=1, full_range=0, chroma_pos=None, scale=None, bias=None, linear_light=False):
     """Fills a float32 / float16 torch tensor with the rectangle `crop` = (x0, y0, w, h) of the picture (None: all of it) at the TENSOR's size, through
     the tables of `colour` (Context.colour / Context.colour_for): DevicePicture.export_rgb_colour_reduced.  Shape (3, h, w) gets R, G, B planes,
     (h, w, 3) / (h, w, 4) packed RGB / RGBA; h x w may be up to 256 times smaller than the crop on either axis, or larger.  Shape and stride rules are
     export_to_tensor's: a device tensor, unit stride along a row, the channels of a packed tensor next to each other, and a shape that reads both
-    ways, (3, n, 3) or (3, n, 4), raises ValueError.  Returns the surface."""
+    ways, (3, n, 3) or (3, n, 4), raises ValueError.  `linear_light=True` scales in linear light: DevicePicture.export_rgb_linear_reduced.
+    Returns the surface."""
     if colour is None:
         raise ValueError("export_colour_to_tensor needs a colour handle")
     if tensor.dim() != 3:
@@ -507,15 +524,16 @@ def export_colour_to_tensor(pic, tensor, colour, crop=None, matrix=1, full_range
         h, w = shape[1], shape[2]
         fmt, ptrs, strides = SURFACE_RGB_PLANAR, [tensor[k].data_ptr() for k in range(3)], [tensor.stride(1) * es] * 3
     s = Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, _colour_sample(tensor), matrix, full_range)
-    pic.export_rgb_colour_reduced(s, colour, crop, chroma_pos or 0, scale, bias)
+    (pic.export_rgb_linear_reduced if linear_light else pic.export_rgb_colour_reduced)(s, colour, crop, chroma_pos or 0, scale, bias)
     return s
 
 
-def export_colour_batch_to_tensor(pics, tensor, colour, crops=None, matrix=1, full_range=0, chroma_pos=None, scale=None, bias=None):
+def export_colour_batch_to_tensor(pics, tensor, colour, crops=None, matrix=1, full_range=0, chroma_pos=None, scale=None, bias=None, linear_light=False):
     """Fills one float32 / float16 torch tensor with N pictures (or N regions: pictures may repeat) through Context.export_rgb_colour_reduced_batch:
     `tensor` of shape (N, 3, h, w) gets R, G, B planes, (N, h, w, 3) / (N, h, w, 4) packed RGB / RGBA; crops[k] = (x0, y0, w, h) (`crops` None: the
     whole picture) is the rectangle of pics[k] that goes to h x w, at any ratio up to 256:1 down and any size up, through the tables of `colour`.
-    Shape and stride rules are export_batch_to_tensor's.  Returns the surfaces."""
+    Shape and stride rules are export_batch_to_tensor's.  `linear_light=True` scales in linear light: Context.export_rgb_linear_reduced_batch.
+    Returns the surfaces."""
     if colour is None:
         raise ValueError("export_colour_batch_to_tensor needs a colour handle")
     if tensor.dim() != 4:
@@ -545,7 +563,8 @@ def export_colour_batch_to_tensor(pics, tensor, colour, crops=None, matrix=1, fu
         ptrs, strides = ([t.data_ptr()], [t.stride(0) * es]) if hwc else ([t[c].data_ptr() for c in range(3)], [t.stride(1) * es] * 3)
         surfaces.append(Surface.wrap(pic.ctx, ptrs, strides, w, h, pic.layout, pic.bpc, fmt, sample, matrix, full_range))
     if n:
-        pics[0].ctx.export_rgb_colour_reduced_batch(surfaces, pics, colour, crops, chroma_pos or 0, scale, bias)
+        ctx = pics[0].ctx
+        (ctx.export_rgb_linear_reduced_batch if linear_light else ctx.export_rgb_colour_reduced_batch)(surfaces, pics, colour, crops, chroma_pos or 0, scale, bias)
     return surfaces
 
 
@@ -722,7 +741,14 @@ class Context:
     def colour_destroy(self, h):
         _chk(self.lib.dav1d_hip_colour_destroy(self.h, h), "colour_destroy")
 
-    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None, _reduced=False, _colour=None):
+    def colour_light_table(self, h, bpc):
+        """dav1d_hip_colour_light_table: (q, e) of a handle of `bpc` bits — the light table in fixed point of the linear-light exports, q[v] =
+        rint(lin[v] 2^(31 - e)) as uint32; HipError where the handle has none (a lin with a negative entry).  Waits."""
+        q, e = np.empty(1 << bpc, np.uint32), C.c_int(0)
+        _chk(self.lib.dav1d_hip_colour_light_table(self.h, h, q.ctypes.data, C.byref(e)), "colour_light_table")
+        return q, e.value
+
+    def export_rgb_scaled_batch(self, surfaces, pics, crops=None, chroma_pos=0, scale=None, bias=None, _filter=None, _reduced=False, _colour=None, _linear=False):
         """dav1d_hip_surface_export_rgb_scaled_batch: item k gets what pics[k].export_rgb_scaled(surfaces[k], crops[k], chroma_pos, scale, bias) writes,
         all items in one launch (two when raster and twin-only pictures are mixed).  Pictures may repeat; `crops` is None (every item whole) or a
         rectangle (x0, y0, w, h) per item.  One format, one sample type and one pixel size (8 bit, or 10 / 12 bit) per batch.  Asynchronous like
@@ -735,7 +761,10 @@ class Context:
         rects = None if crops is None else (SurfaceRect * max(n, 1))(*[SurfaceRect(*[int(v) for v in r]) for r in crops])
         p = DevicePicture._rgb_params(chroma_pos, scale, bias)
         bad = C.c_int(-1)
-        if _colour is not None:
+        if _linear:
+            rc = self.lib.dav1d_hip_surface_export_rgb_linear_reduced_batch(self.h, n, dst, src, rects, C.byref(p), _colour, int(_filter), C.byref(bad))
+            what = "surface_export_rgb_linear_reduced_batch"
+        elif _colour is not None:
             rc = self.lib.dav1d_hip_surface_export_rgb_colour_reduced_batch(self.h, n, dst, src, rects, C.byref(p), _colour, int(_filter), C.byref(bad))
             what = "surface_export_rgb_colour_reduced_batch"
         elif _reduced:
@@ -766,6 +795,13 @@ class Context:
         if colour is None:
             raise ValueError("export_rgb_colour_reduced_batch needs a colour handle")
         self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter, _colour=colour)
+
+    def export_rgb_linear_reduced_batch(self, surfaces, pics, colour, crops=None, chroma_pos=0, scale=None, bias=None, filter=RESIZE_BILINEAR):
+        """dav1d_hip_surface_export_rgb_linear_reduced_batch: item k gets what pics[k].export_rgb_linear_reduced(surfaces[k], colour, crops[k],
+        chroma_pos, scale, bias, filter=filter) writes — scaling in linear light, many items per launch.  One handle serves all items."""
+        if colour is None:
+            raise ValueError("export_rgb_linear_reduced_batch needs a colour handle")
+        self.export_rgb_scaled_batch(surfaces, pics, crops, chroma_pos, scale, bias, _filter=filter, _colour=colour, _linear=True)
 
     # ---- batched entry points (host task arrays, device arenas)
     def itx_add_batch(self, dst, tasks, coef):

@@ -9,6 +9,7 @@ struct Dav1dHipColour {
     int has_matrix, has_enc;
     float m[9];
     unsigned bytes;         // of dev: the LDS of a launch
+    int has_q, qe;          // behind them in dev (surface_linear.hip): q[v] = rint(lin[v] 2^(31 - qe)), 1 << bpc words, where no lin is negative
 };
 
 namespace {
@@ -58,7 +59,10 @@ template <typename Out> struct ColourFn {
     }
     __device__ __forceinline__ void operator()(const int r, const int g, const int b, T &R, T &G, T &B) const {
         const int mask = k.n_lin - 1;          // (a sample above max in a picture that is not one must not read past the table)
-        const float l0 = lin[r & mask], l1 = lin[g & mask], l2 = lin[b & mask];
+        light(lin[r & mask], lin[g & mask], lin[b & mask], R, G, B);
+    }
+    // steps 2 to 4, from the light of a pixel
+    __device__ __forceinline__ void light(const float l0, const float l1, const float l2, T &R, T &G, T &B) const {
         float o0 = l0, o1 = l1, o2 = l2;
         if (k.has_matrix) { o0 = row_5r(k.m, l0, l1, l2); o1 = row_5r(k.m + 3, l0, l1, l2); o2 = row_5r(k.m + 6, l0, l1, l2); }
         if (enc) { o0 = encoded(o0); o1 = encoded(o1); o2 = encoded(o2); }

@@ -73,15 +73,28 @@ extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourD
     if (h->has_matrix) memcpy(h->m, d->m, sizeof(h->m));
     const size_t lin_bytes = (size_t) n_lin * sizeof(float);
     h->bytes = (unsigned) (lin_bytes + (h->has_enc ? ENC_BYTES : 0));
-    std::vector<uint8_t> host(h->bytes, 0);
+    // the light table in fixed point of the linear-light exports (surface_linear.hip): behind the tables, in the same allocation
+    float top = 0.0f;
+    h->has_q = 1;
+    for (int i = 0; i < n_lin; i++) {
+        if (d->lin[i] < 0.0f) h->has_q = 0;
+        if (d->lin[i] > top) top = d->lin[i];
+    }
+    if (top > 0.0f) (void) frexp((double) top, &h->qe);
+    const size_t all_bytes = h->bytes + (h->has_q ? lin_bytes : 0);
+    std::vector<uint8_t> host(all_bytes, 0);
     memcpy(host.data(), d->lin, lin_bytes);
     if (h->has_enc) memcpy(host.data() + lin_bytes, d->enc, DAV1D_HIP_COLOUR_ENC_N * sizeof(uint16_t));
+    if (h->has_q) {
+        uint32_t *const q = reinterpret_cast<uint32_t *>(host.data() + h->bytes);
+        for (int i = 0; i < n_lin; i++) q[i] = (uint32_t) nearbyint(ldexp((double) d->lin[i], 31 - h->qe));          // (a power of two, then one rounding, ties to even: below 2^31)
+    }
     int cur = -1, rc = 0;
     (void) hipGetDevice(&cur);
     if (cur != c->device && hipSetDevice(c->device) != hipSuccess) rc = -ENODEV;
-    if (!rc) rc = hip_rc(hipMalloc((void **) &h->dev, h->bytes));
+    if (!rc) rc = hip_rc(hipMalloc((void **) &h->dev, all_bytes));
     if (!rc) {          // (waits: `host` goes away with this call)
-        rc = hip_rc(hipMemcpyAsync(h->dev, host.data(), h->bytes, hipMemcpyHostToDevice, c->stream));
+        rc = hip_rc(hipMemcpyAsync(h->dev, host.data(), all_bytes, hipMemcpyHostToDevice, c->stream));
         const int rs = hip_rc(hipStreamSynchronize(c->stream));
         if (!rc) rc = rs;
     }
@@ -98,6 +111,16 @@ extern "C" int dav1d_hip_colour_destroy(Dav1dHipContext *c, Dav1dHipColour *h)
     const int rc = hip_rc(hipFree(h->dev));
     delete h;
     return rc;
+}
+
+extern "C" int dav1d_hip_colour_light_table(Dav1dHipContext *c, const Dav1dHipColour *h, uint32_t *q, int *e)
+{
+    if (!c || !h || !q || !e || !h->has_q) return -EINVAL;
+    if (h->device != c->device) return -EXDEV;
+    *e = h->qe;
+    const int rc = hip_rc(hipMemcpyAsync(q, h->dev + h->bytes, sizeof(uint32_t) << h->bpc, hipMemcpyDeviceToHost, c->stream));
+    const int rs = hip_rc(hipStreamSynchronize(c->stream));
+    return rc ? rc : rs;
 }
 
 extern "C" int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipRgbParams *params,

@@ -514,7 +514,8 @@ DAV1D_HIP_API int dav1d_hip_colour_tables(int bpc, int trc_in, int pri_in, int t
  * size; steps 1 to 4 of the definition above, every float operation rounded on its own and nothing fused; the normalisation, alpha 1.0, the matrix,
  * range, I400 and matrix-0 rules; even band rows as in dav1d_hip_surface_export_rgb_reduced.  `filter` is DAV1D_HIP_RESIZE_BILINEAR.
  * The colour stage runs on Q's code values: the pictures are resampled in their own transfer and linearised afterwards.  Scaling in linear light is NOT
- * built (a limitation: an area mean of PQ or gamma codes is darker at high-contrast edges than the mean of the light they stand for); the limitations of
+ * built here (a limitation: an area mean of PQ or gamma codes is darker at high-contrast edges than the mean of the light they stand for;
+ * dav1d_hip_surface_export_rgb_linear_reduced below averages the light); the limitations of
  * dav1d_hip_surface_export_rgb_reduced hold as well.  No film grain.
  * dav1d_hip_surface_rgb_reduced_rows_needed serves this call unchanged: a band [drow0, drow1) reads no source row at or beyond it.
  * Q reaches memory for every item here, whatever its ratio (the tables of the colour stage and the scaler's window do not fit in LDS together): the
@@ -541,6 +542,51 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour_reduced_batch(Dav1dHipCont
                                                                     const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
                                                                     const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */,
                                                                     const Dav1dHipColour *colour, int filter, int *bad_item /* may be NULL */);
+/* Linear-light scaling for the colour-managed export (dav1d_amd/csrc/surface_linear.hip): the calls above resample code values and
+ * linearise afterwards; these linearise at source resolution and average the LIGHT, in one pass, without a full-size float surface.
+ * Definition.  W is the crop window of src taken as a picture of its own (the windows and the crop rule of dav1d_hip_surface_export_scaled: even x0 /
+ * y0 on a subsampled axis).  (R, G, B)(x, y) are the integers dav1d_hip_surface_export_rgb computes for W at its own size — the matrix, range, I400
+ * and matrix-0 rules, chroma_pos 0 / 1 / 2 with cl() against W's chroma size, so no sample outside the crop takes part.
+ *   The light table in fixed point is made once per handle by dav1d_hip_colour_create, on the host, in double: with m the largest entry of lin and
+ *   m = f 2^e, 0.5 <= f < 1 (e = 0 for m == 0), q[v] = (uint32) rint(lin[v] 2^(31 - e)), ties to even — a power-of-two scaling and one rounding,
+ *   q[v] < 2^31.  A handle whose lin holds a negative entry has no q (light is not negative): it is created and serves the other calls as before, and
+ *   these refuse it.  dav1d_hip_colour_light_table copies q and e back (it waits; -EINVAL without q).
+ *   The mean.  wy[j] and wx[o] are the taps and 12-bit weights of R' of dav1d_hip_surface_export_rgb_reduced for the luma axes crop.h -> dst->h and
+ *   crop.w -> dst->w: the area rule S for d <= s up to DAV1D_HIP_SURFACE_REDUCE_MAX : 1, R's one or two taps for d > s; either way they sum to 4096.
+ *   A_c(o, j) = sum over the taps of wy wx q[C_c(x, y)], an exact integer below 2^55: there is NO intermediate rounding (unlike S's t), and no sum
+ *   depends on its order.
+ *   l_c = (float) A_c * 2^(e - 55): uint64 to binary32, ties to even, then an exact power of two.  Results where l is a float32 denormal are not pinned.
+ *   Steps 2, 3 and 4 of dav1d_hip_surface_export_rgb_colour run on l, unchanged; samples F32 and F16 only, formats RGB_PLANAR, RGB_PACKED,
+ *   RGBA_PACKED, alpha 1.0.
+ * Two consequences.  Chroma is sited at SOURCE resolution: the limitation "every plane on its own grid, no phase-corrected chroma" of the scaled
+ * calls does not apply here.  And at d == s on both axes a lin whose entries all lie within a factor 2^7 of its largest gives l == lin[code]: the
+ * bytes are those of dav1d_hip_surface_export_rgb_colour on W.
+ * Limitation: light is kept to 2^(e - 31), absolute — about 5e-6 nit under a 10,000-nit PQ table; the lowest codes of a 12-bit PQ table become 0.
+ * The weights stay 12-bit as in dav1d_hip_surface_export_rgb_reduced.  No film grain.
+ * [drow0, drow1) are destination rows under the family's rule (clamped, even unless the surface's end); a band writes the bytes of the whole-surface
+ * call for its rows.  dav1d_hip_surface_rgb_linear_rows_needed is host arithmetic: with n the luma rows of the picture from the top that rows
+ * [0, drow1) take through wy (crop.y0 + ceil(r s / d) going down, R's rule going up), n where chroma_pos == 0 or the layout does not subsample
+ * rows, else min(crop.y0 + crop.h, n + 2); 0 for drow1 <= 0, a negative errno for what the export refuses.  A band reads no source row at or beyond it.
+ * The batch writes, per item, the bytes of the single call over the whole of dst[i] and no other byte; one params and one colour serve all items;
+ * the uniformity rules and DAV1D_HIP_SURFACE_BATCH_MAX are those of dav1d_hip_surface_export_rgb_colour_reduced_batch.
+ * One streaming kernel: no scratch picture, at most one launch per (raster or twin-only source) x (chroma subsampling present among the items), all
+ * on the context's stream between the events dav1d_hip_last_kernel_ms reads; the items go through the staging ring, for the single call as well; in
+ * the steady state no allocation and no host wait; src is const and a DAV1D_HIP_TWIN_ONLY picture stays one.
+ * Errors, before anything is enqueued or written: those of dav1d_hip_surface_export_rgb_colour_reduced and its batch, in their order, with one more
+ * directly behind "a handle whose bpc is not the picture's": -EINVAL for a handle without q; then -EXDEV as there.  In the batch a NULL colour is a
+ * fault of the whole call (*bad_item = -1). */
+DAV1D_HIP_API int dav1d_hip_colour_light_table(Dav1dHipContext *c, const Dav1dHipColour *h, uint32_t *q /* [1 << bpc] */, int *e);
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_linear_reduced(Dav1dHipContext *c, const Dav1dHipSurface *dst, const Dav1dHipPicture *src,
+                                                              const Dav1dHipSurfaceRect *crop /* NULL = everything */,
+                                                              const Dav1dHipRgbParams *params /* NULL = all zero */, const Dav1dHipColour *colour,
+                                                              int filter, int drow0, int drow1);
+DAV1D_HIP_API int dav1d_hip_surface_export_rgb_linear_reduced_batch(Dav1dHipContext *c, int n, const Dav1dHipSurface *dst /* [n] */,
+                                                                    const Dav1dHipPicture *const *src /* [n] */,
+                                                                    const Dav1dHipSurfaceRect *crop /* [n], or NULL = every item whole */,
+                                                                    const Dav1dHipRgbParams *params /* one for all items, NULL = all zero */,
+                                                                    const Dav1dHipColour *colour, int filter, int *bad_item /* may be NULL */);
+DAV1D_HIP_API int dav1d_hip_surface_rgb_linear_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
+                                                           const Dav1dHipRgbParams *params, int filter, int drow1);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -40,6 +40,10 @@ dav1d_hip_surface_export_rgb_reduced to the same format; 2. dav1d_hip_surface_ex
 (64, 3, 224, 224), against dav1d_hip_surface_export_rgb_reduced_batch; 3. 8K to 3840 x 2160 RGBA float16 against the only other route to those bytes,
 dav1d_hip_surface_export_scaled into a pre-allocated picture + dav1d_hip_surface_export_rgb_colour from it, with dav1d_hip_surface_export_rgb_scaled
 (no colour stage) next to it for what the trip of Q through memory costs.
+--linear-reduced: dav1d_hip_surface_export_rgb_linear_reduced (scaling in linear light) with the same tables, by the same method.  1. the whole 8K picture
+to 224 x 224 planar float16 against dav1d_hip_surface_export_rgb_colour of the whole picture with a lin-only handle into a planar float16 surface (the
+first half of the only other route to the same pixels); 2. its batch, 64 crops of 7168 x 4032 to (64, 3, 224, 224), against the same 64 items as single
+calls; without a bar, both next to dav1d_hip_surface_export_rgb_colour_reduced and its batch, and 8K to 3840 x 2160 RGBA float16.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -653,6 +657,91 @@ def colour_reduced_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def linear_reduced_runs(a, ctx, ev, pics, src_bytes):
+    """dav1d_hip_surface_export_rgb_linear_reduced and its batch.  1.: against the first half of the only other route to the same
+    pixels, dav1d_hip_surface_export_rgb_colour of the whole picture with a lin-only handle into a planar float16 surface (the caller's area mean, matrix
+    and re-encode are not counted).  2.: the batch of 64 against the same 64 items as single calls of the new entry point.  Without a bar: both next to
+    export_rgb_colour_reduced and its batch, which scale code values, and the whole picture at 2:1 to RGBA float16."""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    dw = dh = 224
+    hw, hh = w // 2, h // 2
+    rounds, calls = 1 if a.short else max(a.repeats, 10), min(a.calls, 40)
+    lin, m, enc, has_matrix, has_enc = api.colour_tables(ctx.lib, bpc, 16, 9, 13, 1, 203.0, 1000.0)
+    assert has_matrix and has_enc
+    colour, lin_only = ctx.colour(lin, m, enc, bpc=bpc), ctx.colour(lin, bpc=bpc)
+    P, K4, F16 = api.SURFACE_RGB_PLANAR, api.SURFACE_RGBA_PACKED, api.SAMPLE_F16
+    surfs = [ctx.surface(dw, dh, layout, bpc, P, F16, matrix=9) for _ in range(a.pairs)]
+    fulls = [ctx.surface(w, h, layout, bpc, P, F16, matrix=9) for _ in range(a.pairs)]
+    halves = [ctx.surface(hw, hh, layout, bpc, K4, F16, matrix=9) for _ in range(a.pairs)]
+    out_bytes, q_bytes = 3 * 2 * dw * dh, 2 * (dw * dh + 2 * (dw // 2) * (dh // 2))
+    for p in pics:
+        p.pic.twin_ok = api.TWIN_ONLY
+    runs = []
+    yard = "export_rgb_colour, lin only, to %dx%d planar float16 (yardstick)" % (w, h)
+    runs.append((yard, src_bytes + 3 * 2 * w * h, lambda k: pics[k % a.pairs].export_rgb_colour(fulls[k % a.pairs], lin_only, 1), None))
+    runs.append(("1. export_rgb_linear_reduced to 224x224 planar float16", src_bytes + out_bytes,
+                 lambda k: pics[k % a.pairs].export_rgb_linear_reduced(surfs[k % a.pairs], colour, None, 1), yard))
+    runs.append(("   export_rgb_colour_reduced to 224x224 planar float16 (code values, no bar)", src_bytes + 2 * q_bytes + out_bytes,
+                 lambda k: pics[k % a.pairs].export_rgb_colour_reduced(surfs[k % a.pairs], colour, None, 1), None))
+    n = 64
+    bsurfs = [ctx.surface(dw, dh, layout, bpc, P, F16, matrix=9) for _ in range(n)]
+    cw_, ch_ = min(w, 7168) & ~1, min(h, 4032) & ~1
+    crops = [(((w - cw_) * (k % 8) // 7) & ~1, ((h - ch_) * (k // 8) // 7) & ~1, cw_, ch_) for k in range(n)]
+    bytes_batch = n * (2 * (cw_ * ch_ + 2 * (cw_ // 2) * (ch_ // 2)) + out_bytes)
+
+    def singles(k):
+        for i in range(n):
+            pics[(k + i) % a.pairs].export_rgb_linear_reduced(bsurfs[i], colour, crops[i], 1)
+    yard = "64 single calls in place of the batch: export_rgb_linear_reduced, crops of %dx%d to 224x224 (yardstick)" % (cw_, ch_)
+    runs.append((yard, bytes_batch, singles, None))
+    runs.append(("2. export_rgb_linear_reduced_batch, 64 crops of %dx%d to (64, 3, 224, 224)" % (cw_, ch_), bytes_batch,
+                 lambda k: ctx.export_rgb_linear_reduced_batch(bsurfs, [pics[(k + i) % a.pairs] for i in range(n)], colour, crops, 1), yard))
+    runs.append(("   export_rgb_colour_reduced_batch, the same 64 items (code values, no bar)", bytes_batch + n * 2 * q_bytes,
+                 lambda k: ctx.export_rgb_colour_reduced_batch(bsurfs, [pics[(k + i) % a.pairs] for i in range(n)], colour, crops, 1), None))
+    runs.append(("3. export_rgb_linear_reduced to %dx%d RGBA float16 (no bar)" % (hw, hh), src_bytes + 4 * 2 * hw * hh,
+                 lambda k: pics[k % a.pairs].export_rgb_linear_reduced(halves[k % a.pairs], colour, None, 1), None))
+    print("# surface_bench --linear-reduced on %s: %dx%d 4:2:0 %d-bit twin-only sources, PQ / BT.2020 to sRGB / BT.709 (lin + matrix + enc), %d pictures / surfaces in rotation, "
+          "3 warm-up + %d timed calls per variant and round (batch and its 64 single calls: 4), %d rounds, the variants alternated within a round"
+          % (socket.gethostname(), w, h, bpc, a.pairs, calls, rounds))
+    print("# bytes per call = bytes read + bytes written, from the shapes; device ms between two events around the timed calls; host ms: the clock around issuing them and "
+          "the sync; last ms: dav1d_hip_last_kernel_ms of the last call")
+    results = {r[0]: [] for r in runs}
+    for rnd in range(rounds):
+        for name, nbytes, call, _ in runs:
+            nc = 4 if "batch" in name else calls
+            for k in range(3):
+                call(k)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ev.start()
+            for k in range(nc):
+                call(k)
+            ms = ev.stop_ms() / nc
+            host = (time.perf_counter() - t0) * 1e3 / nc
+            last = ctx.last_kernel_ms()
+            results[name].append((ms, host, last))
+            print("round %2d  %-100s device %8.4f ms/call  host %8.4f  last %8.4f  %7.1f MB/call  %7.0f GB/s" % (rnd, name, ms, host, last, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (median [min .. max] over the rounds)")
+    for name, nbytes, _, _ in runs:
+        cols = [sorted(v[i] for v in results[name]) for i in range(3)]
+        med = [c[len(c) // 2] for c in cols]
+        print("summary   %-100s device %8.4f [%8.4f .. %8.4f]  host %8.4f [%8.4f .. %8.4f]  last %8.4f [%8.4f .. %8.4f] ms   median %7.0f GB/s"
+              % (name, med[0], cols[0][0], cols[0][-1], med[1], cols[1][0], cols[1][-1], med[2], cols[2][0], cols[2][-1], nbytes / med[0] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(x[0] for x in results[name]), sorted(x[0] for x in results[yard])
+        ok = v[len(v) // 2] <= u[len(u) // 2] + (u[-1] - u[0])
+        print("condition %-84s device median %.4f ms <= yardstick median %.4f ms + its spread %.4f ms: %s (x %.2f)"
+              % (name, v[len(v) // 2], u[len(u) // 2], u[-1] - u[0], "met" if ok else "NOT met", u[len(u) // 2] / v[len(v) // 2]))
+    ctx.sync()
+    ctx.colour_destroy(colour)
+    ctx.colour_destroy(lin_only)
+    for s in surfs + fulls + bsurfs + halves + pics:
+        s.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
@@ -664,6 +753,7 @@ def main():
     ap.add_argument("--colour", action="store_true", help="dav1d_hip_surface_export_rgb_colour (PQ / BT.2020 -> sRGB / BT.709) against export_rgb to the same format")
     ap.add_argument("--reduced", action="store_true", help="dav1d_hip_surface_export_rgb_reduced to 224 x 224 against export_scaled 8:1 + export_rgb_resized; a batch of 64")
     ap.add_argument("--colour-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_colour_reduced and its batch against export_rgb_reduced; at 2:1 against export_scaled + export_rgb_colour")
+    ap.add_argument("--linear-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_linear_reduced against a full-size export_rgb_colour; its batch against 64 single calls")
     ap.add_argument("--cells", type=lambda v: [int(x) for x in v.split(",") if x], default=[], help="--colour: variants (a) and (c) again with these values of the option colour_cells")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
@@ -712,6 +802,8 @@ def main():
         return reduced_runs(a, ctx, ev, pics, src_bytes)
     if a.colour_reduced:
         return colour_reduced_runs(a, ctx, ev, pics, src_bytes)
+    if a.linear_reduced:
+        return linear_reduced_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
