@@ -46,6 +46,10 @@ class ColourDesc(C.Structure):         # == Dav1dHipColourDesc
     _fields_ = [("bpc", C.c_int), ("lin", C.POINTER(C.c_float)), ("has_matrix", C.c_int), ("m", C.c_float * 9), ("enc", C.POINTER(C.c_uint16))]
 
 
+class ColourTone(C.Structure):         # == Dav1dHipColourTone
+    _fields_ = [("k", C.c_float * 3), ("gain", C.POINTER(C.c_uint16))]
+
+
 class HostPicture(C.Structure):
     _fields_ = [("data", C.c_void_p * 3), ("stride", C.c_ssize_t * 2), ("dev", Picture), ("alloc", C.c_void_p), ("alloc_size", C.c_size_t)]
 
@@ -111,6 +115,7 @@ SYMBOLS = [
     "dav1d_hip_surface_export_rgb_colour_reduced", "dav1d_hip_surface_export_rgb_colour_reduced_batch",
     "dav1d_hip_surface_export_rgb_linear_reduced", "dav1d_hip_surface_export_rgb_linear_reduced_batch", "dav1d_hip_surface_rgb_linear_rows_needed",
     "dav1d_hip_colour_light_table",
+    "dav1d_hip_colour_create_toned", "dav1d_hip_colour_tables_toned",
 ]
 
 
@@ -334,6 +339,8 @@ def load(path=None):
         "dav1d_hip_surface_export_rgb_linear_reduced_batch": (i, [vp, i, P(Surface), P(P(Picture)), P(SurfaceRect), P(RgbParams), vp, i, P(i)]),
         "dav1d_hip_surface_rgb_linear_rows_needed": (i, [P(Surface), P(Picture), P(SurfaceRect), P(RgbParams), i, i]),
         "dav1d_hip_colour_light_table": (i, [vp, vp, vp, P(i)]),
+        "dav1d_hip_colour_create_toned": (i, [vp, P(ColourDesc), P(ColourTone), P(vp)]),
+        "dav1d_hip_colour_tables_toned": (i, [i, i, i, i, i, C.c_float, C.c_float, vp, vp, P(i), vp, P(i), vp, vp, P(i)]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

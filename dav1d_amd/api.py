@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import FilmGrainData  # noqa: F401
 from ._lib import ITX_TASK, MC_TASK, COMP_TASK, CDEF_TASK, LF_TASK, IPRED_TASK, LR_TASK, WARP_TASK, MC_SCALED_TASK, Picture, HostPicture  # noqa: F401  (re-exported)
 from ._lib import Surface as SurfaceDesc
-from ._lib import SurfaceRect, RgbParams, ColourDesc, COLOUR_ENC_N
+from ._lib import SurfaceRect, RgbParams, ColourDesc, ColourTone, COLOUR_ENC_N
 
 LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
 SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR, SURFACE_RGB_PACKED, SURFACE_RGBA_PACKED = 0, 1, 2, 3, 4      # enum Dav1dHipSurfaceFormat
@@ -346,6 +346,17 @@ def colour_tables(lib, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203
     _chk(lib.dav1d_hip_colour_tables(bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits, lin.ctypes.data, m.ctypes.data, C.byref(has_matrix),
                                      enc.ctypes.data, C.byref(has_enc)), "colour_tables")
     return lin, m.reshape(3, 3), enc, bool(has_matrix.value), bool(has_enc.value)
+
+
+def colour_tables_toned(lib, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203.0, peak_nits=1000.0):
+    """dav1d_hip_colour_tables_toned (host arithmetic, no device): the tables of colour_tables with the tone curve taken out of enc and put into a gain
+    on the pixel's luminance, and the HLG OOTF — lin, m, enc, has_matrix, has_enc, k (3 float32), gain (uint16 bit patterns), has_gain"""
+    lin, m, enc = np.zeros(1 << bpc if bpc in (8, 10, 12) else 1, np.float32), np.zeros(9, np.float32), np.zeros(COLOUR_ENC_N, np.uint16)
+    k, gain = np.zeros(3, np.float32), np.zeros(COLOUR_ENC_N, np.uint16)
+    has_matrix, has_enc, has_gain = C.c_int(0), C.c_int(0), C.c_int(0)
+    _chk(lib.dav1d_hip_colour_tables_toned(bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits, lin.ctypes.data, m.ctypes.data, C.byref(has_matrix),
+                                           enc.ctypes.data, C.byref(has_enc), k.ctypes.data, gain.ctypes.data, C.byref(has_gain)), "colour_tables_toned")
+    return lin, m.reshape(3, 3), enc, bool(has_matrix.value), bool(has_enc.value), k, gain, bool(has_gain.value)
 
 
 def export_to_tensor(pic, tensor, chroma=None, sample=None, matrix=1, full_range=0, row0=0, row1=1 << 30, grain=None, is_id=0, crop=None, resize=False,
@@ -710,10 +721,12 @@ class Context:
     def last_kernel_ms(self):
         return float(self.lib.dav1d_hip_last_kernel_ms(self.h))
 
-    def colour(self, lin, matrix=None, enc=None, bpc=None):
+    def colour(self, lin, matrix=None, enc=None, bpc=None, tone=None):
         """dav1d_hip_colour_create: a handle for DevicePicture.export_rgb_colour from tables of the caller — `lin`: 1 << bpc float32 values (code ->
         linear); `matrix`: None or 9 values, row-major; `enc`: None or COLOUR_ENC_N binary16 bit patterns (uint16, or a float16 array), indexed by the
-        binary16 pattern of the clamped linear value.  Copies the tables to the device and waits.  colour_destroy() frees it."""
+        binary16 pattern of the clamped linear value.  `tone`: None, or (k, gain) of dav1d_hip_colour_create_toned — three luminance coefficients and
+        COLOUR_ENC_N binary16 patterns (uint16 or float16 like enc) indexed by the clamped luminance: the gain that multiplies all three channels
+        in front of the matrix.  Copies the tables to the device and waits.  colour_destroy() frees it."""
         lin = np.ascontiguousarray(lin, dtype=np.float32)
         if bpc is None:
             bpc = int(lin.size).bit_length() - 1
@@ -729,12 +742,28 @@ class Context:
                 raise ValueError("enc has COLOUR_ENC_N entries")
             d.enc = enc.ctypes.data_as(C.POINTER(C.c_uint16))
         h = C.c_void_p()
-        _chk(self.lib.dav1d_hip_colour_create(self.h, C.byref(d), C.byref(h)), "colour_create")
+        if tone is None:
+            _chk(self.lib.dav1d_hip_colour_create(self.h, C.byref(d), C.byref(h)), "colour_create")
+            return h
+        k, gain = tone
+        k = np.asarray(k, dtype=np.float32).reshape(-1)
+        if k.size != 3:
+            raise ValueError("tone is (k, gain) with three coefficients k")
+        gain = np.ascontiguousarray(gain)
+        gain = np.ascontiguousarray(gain.view(np.uint16) if gain.dtype == np.float16 else gain, dtype=np.uint16)
+        if gain.size != COLOUR_ENC_N:
+            raise ValueError("gain has COLOUR_ENC_N entries")
+        t = ColourTone(k=(C.c_float * 3)(*[float(v) for v in k]), gain=gain.ctypes.data_as(C.POINTER(C.c_uint16)))
+        _chk(self.lib.dav1d_hip_colour_create_toned(self.h, C.byref(d), C.byref(t), C.byref(h)), "colour_create_toned")
         return h
 
-    def colour_for(self, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203.0, peak_nits=1000.0):
+    def colour_for(self, bpc, trc_in, pri_in, trc_out=8, pri_out=1, white_nits=203.0, peak_nits=1000.0, luminance=False):
         """dav1d_hip_colour_tables, then colour(): the handle that takes pictures of AV1's transfer / primaries codes trc_in / pri_in to trc_out /
-        pri_out (8: linear light, 1.0 = white_nits)."""
+        pri_out (8: linear light, 1.0 = white_nits).  luminance=True: dav1d_hip_colour_tables_toned — the tone curve as a gain on the pixel's luminance,
+        which keeps the hue of saturated highlights, and the HLG OOTF."""
+        if luminance:
+            lin, m, enc, has_matrix, has_enc, k, gain, has_gain = colour_tables_toned(self.lib, bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits)
+            return self.colour(lin, m if has_matrix else None, enc if has_enc else None, bpc, tone=(k, gain) if has_gain else None)
         lin, m, enc, has_matrix, has_enc = colour_tables(self.lib, bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits)
         return self.colour(lin, m if has_matrix else None, enc if has_enc else None, bpc)
 

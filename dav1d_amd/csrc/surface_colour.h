@@ -10,6 +10,9 @@ struct Dav1dHipColour {
     float m[9];
     unsigned bytes;         // of dev: the LDS of a launch
     int has_q, qe;          // behind them in dev (surface_linear.hip): q[v] = rint(lin[v] 2^(31 - qe)), 1 << bpc words, where no lin is negative
+    int has_tone;           // the tone part (step 1b): gain behind all of that in dev, read from there and never part of `bytes`
+    unsigned gain_off;      // of gain in dev
+    float ky[3];
 };
 
 namespace {
@@ -26,6 +29,8 @@ struct ColourArgs {
     float m[9];
     unsigned n_cells;
     int C;                  // cells a wave takes
+    const uint16_t *gain;   // the tone part of the handle, in global memory; nullptr: none, and step 1b does not exist
+    float ky[3];
 };
 
 // (p0 + p1) + p2 of the products m[j] * l[j], five roundings, nothing contracted into a fused multiply-add
@@ -42,11 +47,26 @@ __device__ __forceinline__ float row_5r(const float *const m, const float l0, co
 #endif
 }
 
+// a * b, one rounding
+__device__ __forceinline__ float mul_1r(const float a, const float b) {
+#ifdef DAV1D_HIP_EMU
+    volatile float p = a * b;
+    return p;
+#else
+#pragma clang fp contract(off)
+    const float p = a * b;
+    return p;
+#endif
+}
+
 __device__ __forceinline__ void put(float &d, const float f) { d = f; }
 __device__ __forceinline__ void put(uint16_t &d, const float f) { d = dv::f32_to_f16_bits(f); }
 
-// the three samples of a pixel from its three integers: the definition of include/dav1d_hip.h, steps 1 to 4
-template <typename Out> struct ColourFn {
+// the three samples of a pixel from its three integers: the definition of include/dav1d_hip.h, steps 1 to 4 (and 1b where the handle has a tone part).
+// TONED = false is the code without step 1b, instruction for instruction: the kernels of surface_colour.hip and surface_colour_reduce.hip are
+// instantiated both ways and the host picks by the handle (a branch on k.gain alone cost their un-toned instances 3 to 13 VGPRs and twelve of them a
+// wave per SIMD); surface_linear.hip, whose registers the branch leaves alone, has the one instance and branches.
+template <typename Out, bool TONED = false> struct ColourFn {
     typedef typename Out::T T;
     const float *lin;
     const uint16_t *enc;    // nullptr: none
@@ -61,8 +81,17 @@ template <typename Out> struct ColourFn {
         const int mask = k.n_lin - 1;          // (a sample above max in a picture that is not one must not read past the table)
         light(lin[r & mask], lin[g & mask], lin[b & mask], R, G, B);
     }
-    // steps 2 to 4, from the light of a pixel
-    __device__ __forceinline__ void light(const float l0, const float l1, const float l2, T &R, T &G, T &B) const {
+    // step 1b: the gain of the pixel's luminance.  One read per pixel at an address the picture chooses, from global memory through the caches
+    // (30 KiB that every wave of the launch reads)
+    __device__ __forceinline__ float gain_of(const float l0, const float l1, const float l2) const {
+        const float y = row_5r(k.ky, l0, l1, l2);
+        const float x = y > 0.0f ? (y < 1.0f ? y : 1.0f) : 0.0f;       // (a NaN fails the first comparison)
+        const unsigned h = dv::f32_to_f16_bits(x) & 0x7fff;            // (x is in [+0, 1]: the mask changes nothing, as in encoded())
+        return dv::f16_bits_to_f32(k.gain[h < 0x3c00u ? h : 0x3c00u]);         // (nor does the bound, which keeps the read inside the allocation whatever a compiler makes of the clamp)
+    }
+    // steps 1b to 4, from the light of a pixel
+    __device__ __forceinline__ void light(float l0, float l1, float l2, T &R, T &G, T &B) const {
+        if (TONED && k.gain) { const float g = gain_of(l0, l1, l2); l0 = mul_1r(l0, g); l1 = mul_1r(l1, g); l2 = mul_1r(l2, g); }
         float o0 = l0, o1 = l1, o2 = l2;
         if (k.has_matrix) { o0 = row_5r(k.m, l0, l1, l2); o1 = row_5r(k.m + 3, l0, l1, l2); o2 = row_5r(k.m + 6, l0, l1, l2); }
         if (enc) { o0 = encoded(o0); o1 = encoded(o1); o2 = encoded(o2); }
@@ -95,6 +124,7 @@ void colour_launch_args(const Dav1dHipRgbParams &p, const Dav1dHipColour *const 
     k.tables = reinterpret_cast<const uint4 *>(h->dev); k.n16 = (int) (h->bytes / 16); k.n_lin = 1 << h->bpc;
     k.has_enc = h->has_enc; k.has_matrix = h->has_matrix; k.normalize = !!p.normalize;
     memcpy(k.m, h->m, sizeof(k.m));
+    if (h->has_tone) { k.gain = reinterpret_cast<const uint16_t *>(h->dev + h->gain_off); memcpy(k.ky, h->ky, sizeof(k.ky)); }
 }
 
 } // namespace

@@ -14,7 +14,7 @@
 
 namespace {
 
-template <typename pixel, bool TILED, int SSH, int SSV, typename Out>
+template <typename pixel, bool TILED, int SSH, int SSV, typename Out, bool TONED>
 __global__ __launch_bounds__(256) void surface_colour_kernel(const RgbxArgs ax, const ColourArgs k, const Out out)
 {
 #ifdef DAV1D_HIP_EMU
@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void surface_colour_kernel(const RgbxArgs ax, 
     for (int i = tid; i < k.n16; i += 256) lds[i] = k.tables[i];
     __syncthreads();
     const float *const lin = reinterpret_cast<const float *>(lds);
-    const ColourFn<Out> fn = { lin, k.has_enc ? reinterpret_cast<const uint16_t *>(lin + k.n_lin) : nullptr, k, out, out.alpha };
+    const ColourFn<Out, TONED> fn = { lin, k.has_enc ? reinterpret_cast<const uint16_t *>(lin + k.n_lin) : nullptr, k, out, out.alpha };
     const unsigned first = (unsigned) blockIdx.x * (unsigned) k.C * 4u + (unsigned) (tid >> 6);
     for (int i = 0; i < k.C; i++) {
         const unsigned cell = first + 4u * (unsigned) i;
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void surface_colour_kernel(const RgbxArgs ax, 
     }
 }
 
-template <typename pixel, bool TILED, typename Out>
+template <typename pixel, bool TILED, typename Out, bool TONED>
 int launch_colour(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const src, void *const *const planes,
                   const Dav1dHipRgbParams &p, const Dav1dHipColour *const h, const int row0, const int row1)
 {
@@ -48,9 +48,9 @@ int launch_colour(Dav1dHipContext *const c, const Dav1dHipSurface *const dst, co
     k.C = c->colour_cells ? c->colour_cells : cells_per_wave(k.n_cells, h->bytes);
     const dim3 grid((k.n_cells + 4u * (unsigned) k.C - 1) / (4u * (unsigned) k.C));
     hipStream_t st = c->stream;
-    if (g.ss_ver) hipLaunchKernelGGL((surface_colour_kernel<pixel, TILED, 1, 1, Out>), grid, dim3(256), h->bytes, st, ax, k, out);
-    else if (g.ss_hor) hipLaunchKernelGGL((surface_colour_kernel<pixel, TILED, 1, 0, Out>), grid, dim3(256), h->bytes, st, ax, k, out);
-    else hipLaunchKernelGGL((surface_colour_kernel<pixel, TILED, 0, 0, Out>), grid, dim3(256), h->bytes, st, ax, k, out);
+    if (g.ss_ver) hipLaunchKernelGGL((surface_colour_kernel<pixel, TILED, 1, 1, Out, TONED>), grid, dim3(256), h->bytes, st, ax, k, out);
+    else if (g.ss_hor) hipLaunchKernelGGL((surface_colour_kernel<pixel, TILED, 1, 0, Out, TONED>), grid, dim3(256), h->bytes, st, ax, k, out);
+    else hipLaunchKernelGGL((surface_colour_kernel<pixel, TILED, 0, 0, Out, TONED>), grid, dim3(256), h->bytes, st, ax, k, out);
     return hip_rc(hipGetLastError());
 }
 
@@ -58,7 +58,7 @@ bool finite_f32(const float f) { uint32_t x; memcpy(&x, &f, 4); return (x & 0x7f
 
 } // namespace
 
-extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourDesc *d, Dav1dHipColour **out)
+extern "C" int dav1d_hip_colour_create_toned(Dav1dHipContext *c, const Dav1dHipColourDesc *d, const Dav1dHipColourTone *t, Dav1dHipColour **out)
 {
     if (!c || !d || !out) return -EINVAL;
     *out = nullptr;
@@ -67,6 +67,11 @@ extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourD
     for (int i = 0; i < n_lin; i++) if (!finite_f32(d->lin[i])) return -EINVAL;
     if (d->has_matrix) for (int i = 0; i < 9; i++) if (!finite_f32(d->m[i])) return -EINVAL;
     if (d->enc) for (int i = 0; i < DAV1D_HIP_COLOUR_ENC_N; i++) if ((d->enc[i] & 0x7c00) == 0x7c00) return -EINVAL;
+    if (t) {
+        if (!t->gain) return -EINVAL;
+        for (int i = 0; i < 3; i++) if (!finite_f32(t->k[i])) return -EINVAL;
+        for (int i = 0; i < DAV1D_HIP_COLOUR_ENC_N; i++) if ((t->gain[i] & 0x7c00) == 0x7c00) return -EINVAL;
+    }
     Dav1dHipColour *const h = new (std::nothrow) Dav1dHipColour();
     if (!h) return -ENOMEM;
     h->device = c->device; h->bpc = d->bpc; h->has_matrix = !!d->has_matrix; h->has_enc = d->enc != nullptr;
@@ -81,7 +86,11 @@ extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourD
         if (d->lin[i] > top) top = d->lin[i];
     }
     if (top > 0.0f) (void) frexp((double) top, &h->qe);
-    const size_t all_bytes = h->bytes + (h->has_q ? lin_bytes : 0);
+    // the gain of the tone part (step 1b): behind all of that, read from there by every kernel — `bytes`, the LDS of a launch, does not know it
+    h->has_tone = t != nullptr;
+    h->gain_off = (unsigned) (h->bytes + (h->has_q ? lin_bytes : 0));
+    if (t) memcpy(h->ky, t->k, sizeof(h->ky));
+    const size_t all_bytes = h->gain_off + (t ? ENC_BYTES : 0);
     std::vector<uint8_t> host(all_bytes, 0);
     memcpy(host.data(), d->lin, lin_bytes);
     if (h->has_enc) memcpy(host.data() + lin_bytes, d->enc, DAV1D_HIP_COLOUR_ENC_N * sizeof(uint16_t));
@@ -89,6 +98,7 @@ extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourD
         uint32_t *const q = reinterpret_cast<uint32_t *>(host.data() + h->bytes);
         for (int i = 0; i < n_lin; i++) q[i] = (uint32_t) nearbyint(ldexp((double) d->lin[i], 31 - h->qe));          // (a power of two, then one rounding, ties to even: below 2^31)
     }
+    if (t) memcpy(host.data() + h->gain_off, t->gain, DAV1D_HIP_COLOUR_ENC_N * sizeof(uint16_t));
     int cur = -1, rc = 0;
     (void) hipGetDevice(&cur);
     if (cur != c->device && hipSetDevice(c->device) != hipSuccess) rc = -ENODEV;
@@ -102,6 +112,11 @@ extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourD
     if (rc) { if (h->dev) (void) hipFree(h->dev); delete h; return rc; }
     *out = h;
     return 0;
+}
+
+extern "C" int dav1d_hip_colour_create(Dav1dHipContext *c, const Dav1dHipColourDesc *d, Dav1dHipColour **out)
+{
+    return dav1d_hip_colour_create_toned(c, d, nullptr, out);
 }
 
 extern "C" int dav1d_hip_colour_destroy(Dav1dHipContext *c, Dav1dHipColour *h)
@@ -142,7 +157,8 @@ extern "C" int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const Dav
     const CallTimer t(c);
     return t.done(with_pixel_state(src->bpc, call.tiled, [&](auto px, auto state) {
         return with_float_out(dst->sample, [&](auto out) {
-            return launch_colour<decltype(px), decltype(state)::value, decltype(out)>(c, dst, src, planes, p, colour, row0, row1);
+            if (colour->has_tone) return launch_colour<decltype(px), decltype(state)::value, decltype(out), true>(c, dst, src, planes, p, colour, row0, row1);
+            return launch_colour<decltype(px), decltype(state)::value, decltype(out), false>(c, dst, src, planes, p, colour, row0, row1);
         });
     }));
 }
@@ -194,6 +210,17 @@ uint16_t f64_to_f16_bits(const double v)
     const int E = ex - 1;
     if (E < -14) return (uint16_t) nearbyint(ldexp(v, 24));                            // subnormal: units of 2^-24 (1024 of them: the smallest normal)
     return (uint16_t) (((E + 15) << 10) + (int) nearbyint((2.0 * f - 1.0) * 1024.0));     // (a carry out of the mantissa goes where it belongs)
+}
+// ... and of any finite v >= 0 below 65520 (the gains of the tone part exceed 1)
+uint16_t f64_to_f16_bits_wide(const double v)
+{
+    if (!(v > 0.0)) return 0;
+    if (v >= 65520.0) return 0x7bff;
+    int ex;
+    const double f = frexp(v, &ex);
+    const int E = ex - 1;
+    if (E < -14) return (uint16_t) nearbyint(ldexp(v, 24));
+    return (uint16_t) (((E + 15) << 10) + (int) nearbyint((2.0 * f - 1.0) * 1024.0));
 }
 double f16_bits_to_f64(const int h) { return h < 0x400 ? ldexp((double) h, -24) : ldexp((double) (0x400 | (h & 0x3ff)), (h >> 10) - 25); }
 
@@ -265,5 +292,30 @@ extern "C" int dav1d_hip_colour_tables(int bpc, int trc_in, int pri_in, int trc_
             const double y = f16_bits_to_f64(h) * p, t = y * (1.0 + y / (p * p)) / (1.0 + y);
             enc[h] = f64_to_f16_bits(linear_to_sdr(trc_out, t));
         }
+    return 0;
+}
+
+extern "C" int dav1d_hip_colour_tables_toned(int bpc, int trc_in, int pri_in, int trc_out, int pri_out, float white_nits, float peak_nits,
+                                             float *lin, float m[9], int *has_matrix, uint16_t *enc, int *has_enc, float k[3], uint16_t *gain, int *has_gain)
+{
+    if (!k || !gain || !has_gain) return -EINVAL;          // (with the other NULL pointers: before any table is written)
+    if (const int rc = dav1d_hip_colour_tables(bpc, trc_in, pri_in, trc_out, pri_out, white_nits, peak_nits, lin, m, has_matrix, enc, has_enc)) return rc;
+    double Min[3][3];
+    (void) rgb_to_xyz(pri_in, Min);          // (a code the call above has accepted)
+    const double p = (double) peak_nits / (double) white_nits;
+    const double gamma = trc_in == 18 ? 1.2 + 0.42 * log10((double) peak_nits / 1000.0) : 1.0;
+    for (int j = 0; j < 3; j++) k[j] = (float) (trc_out == 8 ? Min[1][j] / p : Min[1][j]);
+    if (trc_out == 8) {
+        *has_gain = trc_in == 18;
+        for (int h = 0; h < DAV1D_HIP_COLOUR_ENC_N; h++) gain[h] = *has_gain ? f64_to_f16_bits_wide(pow(f16_bits_to_f64(h), gamma - 1.0)) : 0x3c00;
+        return 0;
+    }
+    *has_gain = 1;
+    gain[0] = gamma > 1.0 ? 0 : f64_to_f16_bits_wide(gamma == 1.0 ? p : 65504.0);          // the limit of tone(d(x) p) / x (below gamma 1 it has none: the largest half)
+    for (int h = 1; h < DAV1D_HIP_COLOUR_ENC_N; h++) {
+        const double x = f16_bits_to_f64(h), y = pow(x, gamma) * p, t = y * (1.0 + y / (p * p)) / (1.0 + y);
+        gain[h] = f64_to_f16_bits_wide(t / x);
+    }
+    for (int h = 0; h < DAV1D_HIP_COLOUR_ENC_N; h++) enc[h] = f64_to_f16_bits(linear_to_sdr(trc_out, f16_bits_to_f64(h)));          // the pure transfer
     return 0;
 }

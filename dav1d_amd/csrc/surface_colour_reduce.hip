@@ -27,7 +27,7 @@ struct ColourItem {
     unsigned n_cells;           // its 64 x 8 chroma cells
 };
 
-template <typename pixel, int SSH, int SSV, typename Out>
+template <typename pixel, int SSH, int SSV, typename Out, bool TONED>
 __global__ __launch_bounds__(256) void surface_colour_batch_kernel(const ColourItem *const __restrict__ items, const uint32_t *const __restrict__ first, const int n,
                                                                    const ColourArgs k, const Out out)
 {
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void surface_colour_batch_kernel(const ColourI
     for (int i = tid; i < k.n16; i += 256) lds[i] = k.tables[i];
     __syncthreads();
     const float *const lin = reinterpret_cast<const float *>(lds);
-    const ColourFn<Out> fn = { lin, k.has_enc ? reinterpret_cast<const uint16_t *>(lin + k.n_lin) : nullptr, k, out, out.alpha };
+    const ColourFn<Out, TONED> fn = { lin, k.has_enc ? reinterpret_cast<const uint16_t *>(lin + k.n_lin) : nullptr, k, out, out.alpha };
     const uint32_t g = blockIdx.x;
     int lo = 0, hi = n;          // first[lo] <= g < first[hi] (item_of of surface_batch.h, written out: through the helper this kernel's code comes out another)
     while (hi - lo > 1) {
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void surface_colour_batch_kernel(const ColourI
 inline int class_of(const ScaleGeom &g) { return g.ss_hor + g.ss_ver; }
 
 // the checked items of a call (n of them; 1: the single call), every one through its Q
-template <typename pixel, typename Out>
+template <typename pixel, typename Out, bool TONED>
 int colour_reduced_run(Dav1dHipContext *const c, const int n, const Dav1dHipSurface *const dst, const Dav1dHipPicture *const *const src, ReducePlan *const plan,
                        const Dav1dHipRgbParams &p, const Dav1dHipColour *const h)
 {
@@ -92,9 +92,9 @@ int colour_reduced_run(Dav1dHipContext *const c, const int n, const Dav1dHipSurf
                   [&](const int t, const ColourItem *const items, const uint32_t *const first, const int n_t, const uint32_t groups) {
                       const dim3 grid(groups), wg(256);
                       hipStream_t st = c->stream;
-                      if (t == 0) hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 0, 0, Out>), grid, wg, h->bytes, st, items, first, n_t, k, out);
-                      else if (t == 1) hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 0, Out>), grid, wg, h->bytes, st, items, first, n_t, k, out);
-                      else hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 1, Out>), grid, wg, h->bytes, st, items, first, n_t, k, out);
+                      if (t == 0) hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 0, 0, Out, TONED>), grid, wg, h->bytes, st, items, first, n_t, k, out);
+                      else if (t == 1) hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 0, Out, TONED>), grid, wg, h->bytes, st, items, first, n_t, k, out);
+                      else hipLaunchKernelGGL((surface_colour_batch_kernel<pixel, 1, 1, Out, TONED>), grid, wg, h->bytes, st, items, first, n_t, k, out);
                   });
 }
 
@@ -102,7 +102,10 @@ int colour_reduced_run_sample(Dav1dHipContext *const c, const int n, const Dav1d
                               const Dav1dHipRgbParams &p, const Dav1dHipColour *const h)
 {
     return with_pixel(h->bpc, [&](auto px) {
-        return with_float_out(dst[0].sample, [&](auto out) { return colour_reduced_run<decltype(px), decltype(out)>(c, n, dst, src, plan, p, h); });
+        return with_float_out(dst[0].sample, [&](auto out) {
+            if (h->has_tone) return colour_reduced_run<decltype(px), decltype(out), true>(c, n, dst, src, plan, p, h);
+            return colour_reduced_run<decltype(px), decltype(out), false>(c, n, dst, src, plan, p, h);
+        });
     });
 }
 

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void surface_linear_kernel(const LinItem *cons
     for (int i = tid; i < k.n16; i += 256) lds[i] = k.tables[i];          // q
     __syncthreads();          // (before any lane can leave)
     LinLds &L = *reinterpret_cast<LinLds *>(lds + k.n16);
-    const ColourFn<Out> fn = { nullptr, k.has_enc ? enc : nullptr, k, out, out.alpha };
+    const ColourFn<Out, true> fn = { nullptr, k.has_enc ? enc : nullptr, k, out, out.alpha };          // (step 1b behind a branch on k.gain, uniform in the launch)
     const uint32_t g = blockIdx.x;
     const int lo = item_of(first, n, g);
     LinItem it = items[lo];

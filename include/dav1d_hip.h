@@ -494,10 +494,11 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const 
 /* Host arithmetic that fills a Dav1dHipColourDesc from AV1's (H.273) codes: computed in double, rounded once to the table's type, no device involved.
  * lin[v] is the light of code v: the inverse OETF / EOTF of trc_in at v / max — 1, 6, 14, 15: the BT.709 curve; 13: sRGB; 4: gamma 2.2; 8: linear;
  * 16: PQ (ST 2084, absolute, 10000 nits at v = max); 18: HLG, the inverse OETF only, scaled so that v = max is peak_nits (NO OOTF: scene light is
- * shown as display light, a limitation).  SDR transfers give light relative to white_nits (v = max is white_nits).
+ * shown as display light, a limitation; dav1d_hip_colour_tables_toned below applies it).  SDR transfers give light relative to white_nits (v = max is white_nits).
  * The unit: with trc_out == 8 (linear out) 1.0 means white_nits and there is no enc (*has_enc = 0, enc untouched; HDR light exceeds 1.0).  Otherwise
  * 1.0 means peak_nits, and enc[h] = f16(OETF_out(tone(x p))), x the value of half h, p = peak_nits / white_nits, tone(y) = y (1 + y / p^2) / (1 + y)
- * (the identity at p == 1; maps p to 1), applied PER CHANNEL (hues of saturated highlights shift; a luminance-based operator is not built).
+ * (the identity at p == 1; maps p to 1), applied PER CHANNEL (hues of saturated highlights shift; the luminance-based operator is
+ * dav1d_hip_colour_tables_toned below).
  * trc_out: 8, 13, 1 / 6 / 14 / 15, 4.  Primaries 1 (BT.709), 9 (BT.2020), 12 (P3-D65): m = RGB -> XYZ -> RGB from the H.273 chromaticities (all three
  * share D65: no adaptation); equal primaries give *has_matrix = 0 and the identity in m.
  * -ENOTSUP for any other code; -EINVAL for a NULL pointer, a bpc other than 8, 10, 12, white_nits <= 0 or peak_nits < white_nits (or not finite).
@@ -505,6 +506,49 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_colour(Dav1dHipContext *c, const 
 DAV1D_HIP_API int dav1d_hip_colour_tables(int bpc, int trc_in, int pri_in, int trc_out, int pri_out, float white_nits, float peak_nits,
                                           float *lin /* [1 << bpc] */, float m[9], int *has_matrix,
                                           uint16_t *enc /* [DAV1D_HIP_COLOUR_ENC_N] */, int *has_enc);
+/* The tone part of a handle (dav1d_amd/csrc/surface_colour.h): a gain that depends on the pixel's LUMINANCE and multiplies all
+ * three channels, so that the ratios between them — the hue — stay what they were.  It serves a hue-preserving tone operator, RGB' = RGB tone(Y) / Y,
+ * and BT.2100's HLG OOTF, F_D = alpha Y_S^(gamma - 1) E_S, alike.
+ * Definition.  A handle made by dav1d_hip_colour_create_toned with a non-NULL `t` carries three float32 coefficients k[3] and a table `gain` of
+ * DAV1D_HIP_COLOUR_ENC_N binary16 bit patterns.  With such a handle EVERY export that takes a handle — dav1d_hip_surface_export_rgb_colour,
+ * dav1d_hip_surface_export_rgb_colour_reduced, dav1d_hip_surface_export_rgb_linear_reduced and the two batches — runs step 1b between step 1
+ * (l_c = lin[code_c]; in the linear-light calls l_c = (float) A_c 2^(e - 55)) and step 2 (the matrix).  In float32, every operation rounded on its
+ * own, nothing fused:
+ *   1b. p_j = k[j] * l_j, Y = (p_0 + p_1) + p_2 (the five roundings of a matrix row); x = Y > 0 ? (Y < 1 ? Y : 1) : 0 (negative values, -0.0 and NaN
+ *       give +0, as in step 3); h = the binary16 bit pattern of x (ties to even, subnormals kept: 0 <= h <= 0x3C00); g = the float32 value of the
+ *       binary16 gain[h]; l'_c = l_c * g, one rounding per channel.  Steps 2, 3 and 4 run on l', unchanged.
+ * Without a tone part (t == NULL, and every handle of dav1d_hip_colour_create, which is that case) step 1b does not exist and the bytes are what they
+ * were.  Results whose intermediates are float32 denormals are not pinned, as above.
+ * The gain sits in front of the matrix because a scalar gain commutes with it, luminance is taken with the coefficients of the SOURCE primaries —
+ * where l lives — and the HLG OOTF is defined there.  k is scaled by the caller so that the index range [0, 1] is the range it means.
+ * The table lives in the handle's one device allocation behind what was there and is read from global memory, once per pixel: the LDS, the launch
+ * shape and the light table of a launch are those of the un-toned handle, dav1d_hip_live_objects counts what it counted, and no entry point gains an
+ * argument or an error.
+ * dav1d_hip_colour_create_toned refuses everything dav1d_hip_colour_create refuses, with its code and in its order; then -EINVAL for a non-NULL t
+ * with a NULL gain, for a k entry that is not finite, for a gain entry with all exponent bits set (either sign is allowed, as in enc).
+ * dav1d_hip_colour_tables_toned (host arithmetic, double, each entry rounded once to its type): codes, refusals (and -EINVAL for a NULL k, gain or
+ * has_gain), lin, m, has_matrix and the unit are those of dav1d_hip_colour_tables.  K is the Y row of RGB -> XYZ of pri_in ((0.2627, 0.6780, 0.0593)
+ * for BT.2020); p = peak_nits / white_nits; k = K with trc_out != 8 and K / p with trc_out == 8, so that the index x is luminance in units of
+ * peak_nits either way.  gamma = 1.2 + 0.42 log10(peak_nits / 1000) with trc_in == 18 (BT.2100's extended formula, which the recommendation gives
+ * for roughly 400 to 2000 nits; it is applied as it stands outside that range), else 1; d(x) = x^gamma is display luminance in peak units.
+ *   trc_out == 8: gain[h] = f16(x^(gamma - 1)), the OOTF alone — linear output stays absolute light, nothing is tone-mapped, no enc — and
+ *     *has_gain = (trc_in == 18); for other inputs gain is filled with 1.0 and *has_gain = 0.
+ *   trc_out != 8: gain[h] = f16(tone(d(x) p) / x) for x > 0 and its limit at x == 0 (p for gamma == 1, 0 above; the largest half below), tone the
+ *     curve of dav1d_hip_colour_tables; *has_gain = 1; gain[0x3C00] is 1.0 and gains reach p.  l' is tone-mapped light in white units
+ *     (1.0 = the output's white), and enc[h] = f16(OETF_out(x)) is the pure transfer — the tone curve is NOT in it.
+ * Limitation: after the gain a saturated channel can exceed 1.0 while the luminance does not — a linear-light red of (4.0, 0.4, 0.2) white units
+ * under p = 1000 / 203 becomes (1.95, 0.19, 0.10) — and step 3 clips it per channel.  No desaturation towards white is built.  A caller with a curve
+ * of its own (BT.2390's EETF, say) hands its gain to dav1d_hip_colour_create_toned. */
+typedef struct Dav1dHipColourTone {
+    float k[3];             /* Y = (k[0] l_R + k[1] l_G) + k[2] l_B, scaled so that the gain's index range [0, 1] is the range the caller means */
+    const uint16_t *gain;   /* DAV1D_HIP_COLOUR_ENC_N binary16 bit patterns */
+} Dav1dHipColourTone;
+DAV1D_HIP_API int dav1d_hip_colour_create_toned(Dav1dHipContext *c, const Dav1dHipColourDesc *d, const Dav1dHipColourTone *t /* NULL: dav1d_hip_colour_create */,
+                                                Dav1dHipColour **out);
+DAV1D_HIP_API int dav1d_hip_colour_tables_toned(int bpc, int trc_in, int pri_in, int trc_out, int pri_out, float white_nits, float peak_nits,
+                                                float *lin /* [1 << bpc] */, float m[9], int *has_matrix,
+                                                uint16_t *enc /* [DAV1D_HIP_COLOUR_ENC_N] */, int *has_enc,
+                                                float k[3], uint16_t *gain /* [DAV1D_HIP_COLOUR_ENC_N] */, int *has_gain);
 /* The colour-managed export at ANY size (dav1d_amd/csrc/surface_colour_reduce.hip): crop, resize, reduce and batch with the colour
  * stage behind them.  dav1d_hip_surface_export_rgb_colour keeps refusing a surface of another size; these are entry points of their own.
  * Nothing numerical is new.  Let Q be the picture of dst->w x dst->h samples, of src's layout and bpc, whose planes are R' of the crop windows: exactly

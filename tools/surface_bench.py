@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced | --colour-reduced] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced | --colour-reduced | --linear-reduced | --toned] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -44,6 +44,9 @@ dav1d_hip_surface_export_scaled into a pre-allocated picture + dav1d_hip_surface
 to 224 x 224 planar float16 against dav1d_hip_surface_export_rgb_colour of the whole picture with a lin-only handle into a planar float16 surface (the
 first half of the only other route to the same pixels); 2. its batch, 64 crops of 7168 x 4032 to (64, 3, 224, 224), against the same 64 items as single
 calls; without a bar, both next to dav1d_hip_surface_export_rgb_colour_reduced and its batch, and 8K to 3840 x 2160 RGBA float16.
+--toned: the tone part of a handle (dav1d_hip_colour_create_toned), by the same method: dav1d_hip_surface_export_rgb_colour at full size,
+dav1d_hip_surface_export_rgb_colour_reduced and dav1d_hip_surface_export_rgb_linear_reduced 8K to 224 x 224 and the linear batch of 64, each with the un-toned
+handle of dav1d_hip_colour_tables and with the toned one of dav1d_hip_colour_tables_toned, alternated; the ratio toned / un-toned per call, without a bar.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -742,6 +745,85 @@ def linear_reduced_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def toned_runs(a, ctx, ev, pics, src_bytes):
+    """the tone part of a handle: each of the three single calls and the 64-item linear batch with the un-toned handle of
+    dav1d_hip_colour_tables(10, 16, 9, 13, 1, 203, 1000) and with the toned one of dav1d_hip_colour_tables_toned, alternated within a round.  A
+    library without dav1d_hip_colour_create_toned (the commit before the tone part) runs the un-toned half alone: the same command there gives the
+    yardstick the un-toned calls are held against."""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    dw = dh = 224
+    rounds, calls = 1 if a.short else max(a.repeats, 10), min(a.calls, 40)
+    lin, m, enc, has_matrix, has_enc = api.colour_tables(ctx.lib, bpc, 16, 9, 13, 1, 203.0, 1000.0)
+    assert has_matrix and has_enc
+    handles = [("un-toned", ctx.colour(lin, m, enc, bpc=bpc))]
+    if hasattr(ctx.lib, "dav1d_hip_colour_create_toned"):
+        handles.append(("toned", ctx.colour_for(bpc, 16, 9, 13, 1, 203.0, 1000.0, luminance=True)))
+    P, F16 = api.SURFACE_RGB_PLANAR, api.SAMPLE_F16
+    fulls = [ctx.surface(w, h, layout, bpc, P, F16, matrix=9) for _ in range(a.pairs)]
+    surfs = [ctx.surface(dw, dh, layout, bpc, P, F16, matrix=9) for _ in range(a.pairs)]
+    n = 64
+    bsurfs = [ctx.surface(dw, dh, layout, bpc, P, F16, matrix=9) for _ in range(n)]
+    cw_, ch_ = min(w, 7168) & ~1, min(h, 4032) & ~1
+    crops = [(((w - cw_) * (k % 8) // 7) & ~1, ((h - ch_) * (k // 8) // 7) & ~1, cw_, ch_) for k in range(n)]
+    out_bytes, q_bytes = 3 * 2 * dw * dh, 2 * (dw * dh + 2 * (dw // 2) * (dh // 2))
+    bytes_batch = n * (2 * (cw_ * ch_ + 2 * (cw_ // 2) * (ch_ // 2)) + out_bytes)
+    for p in pics:
+        p.pic.twin_ok = api.TWIN_ONLY
+    runs = []
+    for hname, hd in handles:
+        yard = None if hname == "un-toned" else lambda name: name.replace("toned", "un-toned", 1)
+        for name, nbytes, call in (
+                ("1. export_rgb_colour to %dx%d planar float16, %s" % (w, h, hname), src_bytes + 3 * 2 * w * h,
+                 lambda k, hd=hd: pics[k % a.pairs].export_rgb_colour(fulls[k % a.pairs], hd, 1)),
+                ("2. export_rgb_colour_reduced to 224x224 planar float16, %s" % hname, src_bytes + 2 * q_bytes + out_bytes,
+                 lambda k, hd=hd: pics[k % a.pairs].export_rgb_colour_reduced(surfs[k % a.pairs], hd, None, 1)),
+                ("3. export_rgb_linear_reduced to 224x224 planar float16, %s" % hname, src_bytes + out_bytes,
+                 lambda k, hd=hd: pics[k % a.pairs].export_rgb_linear_reduced(surfs[k % a.pairs], hd, None, 1)),
+                ("4. export_rgb_linear_reduced_batch, 64 crops of %dx%d to (64, 3, 224, 224), %s" % (cw_, ch_, hname), bytes_batch,
+                 lambda k, hd=hd: ctx.export_rgb_linear_reduced_batch(bsurfs, [pics[(k + i) % a.pairs] for i in range(n)], hd, crops, 1))):
+            runs.append((name, nbytes, call, yard(name) if yard else None))
+    runs.sort(key=lambda r: (r[0][:2], r[3] is not None))          # a call with the un-toned handle, then the same call with the toned one
+    print("# surface_bench --toned on %s: %dx%d 4:2:0 %d-bit twin-only sources, PQ / BT.2020 to sRGB / BT.709 (lin + matrix + enc; toned: the curve as a gain on the luminance), "
+          "chroma_pos 1, %d pictures / surfaces in rotation, 3 warm-up + %d timed calls per variant and round (batch: 4), %d rounds, the variants alternated within a round"
+          % (socket.gethostname(), w, h, bpc, a.pairs, calls, rounds))
+    print("# bytes per call = bytes read + bytes written, from the shapes (tables not counted); device ms between two events around the timed calls; host ms: the clock around "
+          "issuing them and the sync; last ms: dav1d_hip_last_kernel_ms of the last call")
+    results = {r[0]: [] for r in runs}
+    for rnd in range(rounds):
+        for name, nbytes, call, _ in runs:
+            nc = 4 if "batch" in name else calls
+            for k in range(3):
+                call(k)
+            ctx.sync()
+            t0 = time.perf_counter()
+            ev.start()
+            for k in range(nc):
+                call(k)
+            ms = ev.stop_ms() / nc
+            host = (time.perf_counter() - t0) * 1e3 / nc
+            last = ctx.last_kernel_ms()
+            results[name].append((ms, host, last))
+            print("round %2d  %-100s device %8.4f ms/call  host %8.4f  last %8.4f  %7.1f MB/call  %7.0f GB/s" % (rnd, name, ms, host, last, nbytes / 1e6, nbytes / ms / 1e6))
+    print("# summary (median [min .. max] over the rounds)")
+    for name, nbytes, _, _ in runs:
+        cols = [sorted(v[i] for v in results[name]) for i in range(3)]
+        med = [c[len(c) // 2] for c in cols]
+        print("summary   %-100s device %8.4f [%8.4f .. %8.4f]  host %8.4f [%8.4f .. %8.4f]  last %8.4f [%8.4f .. %8.4f] ms   median %7.0f GB/s"
+              % (name, med[0], cols[0][0], cols[0][-1], med[1], cols[1][0], cols[1][-1], med[2], cols[2][0], cols[2][-1], nbytes / med[0] / 1e6))
+    for name, _, _, yard in runs:
+        if yard is None:
+            continue
+        v, u = sorted(x[0] for x in results[name]), sorted(x[0] for x in results[yard])
+        print("ratio     %-100s device median %.4f ms / un-toned median %.4f ms = %.3f (no bar; the un-toned call spreads over %.4f ms)"
+              % (name, v[len(v) // 2], u[len(u) // 2], v[len(v) // 2] / u[len(u) // 2], u[-1] - u[0]))
+    ctx.sync()
+    for _, hd in handles:
+        ctx.colour_destroy(hd)
+    for s in fulls + surfs + bsurfs + pics:
+        s.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
@@ -754,6 +836,7 @@ def main():
     ap.add_argument("--reduced", action="store_true", help="dav1d_hip_surface_export_rgb_reduced to 224 x 224 against export_scaled 8:1 + export_rgb_resized; a batch of 64")
     ap.add_argument("--colour-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_colour_reduced and its batch against export_rgb_reduced; at 2:1 against export_scaled + export_rgb_colour")
     ap.add_argument("--linear-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_linear_reduced against a full-size export_rgb_colour; its batch against 64 single calls")
+    ap.add_argument("--toned", action="store_true", help="the three colour-managed single calls and the linear batch of 64 with an un-toned and a toned handle, alternated")
     ap.add_argument("--cells", type=lambda v: [int(x) for x in v.split(",") if x], default=[], help="--colour: variants (a) and (c) again with these values of the option colour_cells")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
@@ -804,6 +887,8 @@ def main():
         return colour_reduced_runs(a, ctx, ev, pics, src_bytes)
     if a.linear_reduced:
         return linear_reduced_runs(a, ctx, ev, pics, src_bytes)
+    if a.toned:
+        return toned_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
