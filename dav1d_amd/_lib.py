@@ -50,6 +50,10 @@ class ColourTone(C.Structure):         # == Dav1dHipColourTone
     _fields_ = [("k", C.c_float * 3), ("gain", C.POINTER(C.c_uint16))]
 
 
+class LightStatsData(C.Structure):     # == Dav1dHipLightStatsData
+    _fields_ = [("n", C.c_uint64), ("n_above", C.c_uint64), ("n_nonpos", C.c_uint64), ("max_light", C.c_float), ("hist", C.c_uint64 * COLOUR_ENC_N)]
+
+
 class HostPicture(C.Structure):
     _fields_ = [("data", C.c_void_p * 3), ("stride", C.c_ssize_t * 2), ("dev", Picture), ("alloc", C.c_void_p), ("alloc_size", C.c_size_t)]
 
@@ -116,6 +120,8 @@ SYMBOLS = [
     "dav1d_hip_surface_export_rgb_linear_reduced", "dav1d_hip_surface_export_rgb_linear_reduced_batch", "dav1d_hip_surface_rgb_linear_rows_needed",
     "dav1d_hip_colour_light_table",
     "dav1d_hip_colour_create_toned", "dav1d_hip_colour_tables_toned",
+    "dav1d_hip_light_stats_create", "dav1d_hip_light_stats_destroy", "dav1d_hip_light_stats_alive", "dav1d_hip_light_stats_reset", "dav1d_hip_picture_light_stats",
+    "dav1d_hip_light_stats_read", "dav1d_hip_light_stats_rank", "dav1d_hip_light_stats_mean", "dav1d_hip_colour_update_tone",
 ]
 
 
@@ -341,6 +347,15 @@ def load(path=None):
         "dav1d_hip_colour_light_table": (i, [vp, vp, vp, P(i)]),
         "dav1d_hip_colour_create_toned": (i, [vp, P(ColourDesc), P(ColourTone), P(vp)]),
         "dav1d_hip_colour_tables_toned": (i, [i, i, i, i, i, C.c_float, C.c_float, vp, vp, P(i), vp, P(i), vp, vp, P(i)]),
+        "dav1d_hip_light_stats_create": (i, [vp, P(vp)]),
+        "dav1d_hip_light_stats_destroy": (i, [vp, vp]),
+        "dav1d_hip_light_stats_alive": (C.c_longlong, []),
+        "dav1d_hip_light_stats_reset": (i, [vp, vp]),
+        "dav1d_hip_picture_light_stats": (i, [vp, vp, P(Picture), P(SurfaceRect), i, i, i, vp, P(C.c_float), i, i]),
+        "dav1d_hip_light_stats_read": (i, [vp, vp, P(LightStatsData)]),
+        "dav1d_hip_light_stats_rank": (i, [P(LightStatsData), C.c_uint64, P(i)]),
+        "dav1d_hip_light_stats_mean": (C.c_double, [P(LightStatsData)]),
+        "dav1d_hip_colour_update_tone": (i, [vp, vp, P(ColourTone)]),
         "dav1d_hip_dsp_init_8bpc": (i, [vp]),
         "dav1d_hip_dsp_init_16bpc": (i, [vp, i]),
     }

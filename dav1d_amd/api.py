@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import FilmGrainData  # noqa: F401
 from ._lib import ITX_TASK, MC_TASK, COMP_TASK, CDEF_TASK, LF_TASK, IPRED_TASK, LR_TASK, WARP_TASK, MC_SCALED_TASK, Picture, HostPicture  # noqa: F401  (re-exported)
 from ._lib import Surface as SurfaceDesc
-from ._lib import SurfaceRect, RgbParams, ColourDesc, ColourTone, COLOUR_ENC_N
+from ._lib import SurfaceRect, RgbParams, ColourDesc, ColourTone, LightStatsData, COLOUR_ENC_N
 
 LAYOUT_I400, LAYOUT_I420, LAYOUT_I422, LAYOUT_I444 = 0, 1, 2, 3
 SURFACE_PLANAR, SURFACE_SEMIPLANAR, SURFACE_RGB_PLANAR, SURFACE_RGB_PACKED, SURFACE_RGBA_PACKED = 0, 1, 2, 3, 4      # enum Dav1dHipSurfaceFormat
@@ -655,6 +655,73 @@ class _ReconList:
             self.h = None
 
 
+def _tone_of(tone):
+    """(k, gain) as a ColourTone, and the array it points into (to be kept alive for the call)"""
+    k, gain = tone
+    k = np.asarray(k, dtype=np.float32).reshape(-1)
+    if k.size != 3:
+        raise ValueError("tone is (k, gain) with three coefficients k")
+    gain = np.ascontiguousarray(gain)
+    gain = np.ascontiguousarray(gain.view(np.uint16) if gain.dtype == np.float16 else gain, dtype=np.uint16)
+    if gain.size != COLOUR_ENC_N:
+        raise ValueError("gain has COLOUR_ENC_N entries")
+    return ColourTone(k=(C.c_float * 3)(*[float(v) for v in k]), gain=gain.ctypes.data_as(C.POINTER(C.c_uint16))), gain
+
+
+class LightStats:
+    """Per-picture light statistics on the device (dav1d_hip_light_stats_*, include/dav1d_hip.h): a histogram of luminance over the index of a toned
+    handle's gain, with the pixels above 1.0, the pixels at or below 0 and the largest light.  add() accumulates without waiting; read() waits."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _chk(ctx.lib.dav1d_hip_light_stats_create(ctx.h, C.byref(self.h)), "light_stats_create")
+        self._data = None
+
+    def reset(self):
+        _chk(self.ctx.lib.dav1d_hip_light_stats_reset(self.ctx.h, self.h), "light_stats_reset")
+        self._data = None
+
+    def add(self, pic, colour, k, crop=None, matrix=1, full_range=0, chroma_pos=0, row0=0, row1=1 << 30):
+        """dav1d_hip_picture_light_stats: counts luma rows [row0, row1) of the rectangle crop = (x0, y0, w, h) of `pic` (None: all of it), its codes
+        linearised by the handle `colour`, its luminance weighed by the three coefficients k."""
+        k = np.asarray(k, dtype=np.float32).reshape(-1)
+        if k.size != 3:
+            raise ValueError("k has three coefficients")
+        _chk(self.ctx.lib.dav1d_hip_picture_light_stats(self.ctx.h, self.h, C.byref(pic.pic), DevicePicture._rect(crop), matrix, full_range, chroma_pos, colour,
+                                                        (C.c_float * 3)(*[float(v) for v in k]), row0, row1), "picture_light_stats")
+        self._data = None
+
+    def _read(self):
+        if self._data is None:
+            d = LightStatsData()
+            _chk(self.ctx.lib.dav1d_hip_light_stats_read(self.ctx.h, self.h, C.byref(d)), "light_stats_read")
+            self._data = d
+        return self._data
+
+    def read(self):
+        """dav1d_hip_light_stats_read: {"n", "n_above", "n_nonpos" (ints), "max_light" (float32), "hist" (uint64 array of COLOUR_ENC_N)}.  Waits."""
+        d = self._read()
+        return {"n": int(d.n), "n_above": int(d.n_above), "n_nonpos": int(d.n_nonpos), "max_light": np.float32(d.max_light),
+                "hist": np.ctypeslib.as_array(d.hist).astype(np.uint64)}
+
+    def rank(self, fraction):
+        """the bin that holds the pixel of rank max(1, ceil(fraction * n)) counted from the darkest (dav1d_hip_light_stats_rank); 0.999: the 99.9th percentile"""
+        d = self._read()
+        h = C.c_int(-1)
+        _chk(self.ctx.lib.dav1d_hip_light_stats_rank(C.byref(d), max(1, int(np.ceil(fraction * int(d.n)))), C.byref(h)), "light_stats_rank")
+        return h.value
+
+    def mean(self):
+        """dav1d_hip_light_stats_mean: the mean of the bins' values, in the unit of the index"""
+        return float(self.ctx.lib.dav1d_hip_light_stats_mean(C.byref(self._read())))
+
+    def free(self):
+        if self.h:
+            _chk(self.ctx.lib.dav1d_hip_light_stats_destroy(self.ctx.h, self.h), "light_stats_destroy")
+            self.h = C.c_void_p()
+
+
 class Context:
     """dav1d_hip_open() wrapper.  `stream` is a raw hipStream_t (int) or None."""
 
@@ -745,15 +812,7 @@ class Context:
         if tone is None:
             _chk(self.lib.dav1d_hip_colour_create(self.h, C.byref(d), C.byref(h)), "colour_create")
             return h
-        k, gain = tone
-        k = np.asarray(k, dtype=np.float32).reshape(-1)
-        if k.size != 3:
-            raise ValueError("tone is (k, gain) with three coefficients k")
-        gain = np.ascontiguousarray(gain)
-        gain = np.ascontiguousarray(gain.view(np.uint16) if gain.dtype == np.float16 else gain, dtype=np.uint16)
-        if gain.size != COLOUR_ENC_N:
-            raise ValueError("gain has COLOUR_ENC_N entries")
-        t = ColourTone(k=(C.c_float * 3)(*[float(v) for v in k]), gain=gain.ctypes.data_as(C.POINTER(C.c_uint16)))
+        t, _keep = _tone_of(tone)
         _chk(self.lib.dav1d_hip_colour_create_toned(self.h, C.byref(d), C.byref(t), C.byref(h)), "colour_create_toned")
         return h
 
@@ -769,6 +828,17 @@ class Context:
 
     def colour_destroy(self, h):
         _chk(self.lib.dav1d_hip_colour_destroy(self.h, h), "colour_destroy")
+
+    def colour_update_tone(self, h, tone):
+        """dav1d_hip_colour_update_tone: replaces the tone part of the live handle `h` (one made with tone=) by tone = (k, gain), in stream order
+        and without waiting: exports enqueued before use the old part, exports enqueued after the new one.  The arrays may be reused on return."""
+        t, _keep = _tone_of(tone)          # (_keep: the array t.gain points into, which may be a copy made here, lives until the call has returned)
+        _chk(self.lib.dav1d_hip_colour_update_tone(self.h, h, C.byref(t)), "colour_update_tone")
+        del _keep
+
+    def light_stats(self):
+        """dav1d_hip_light_stats_create: a zeroed accumulator of per-picture light statistics on this context's device (LightStats)."""
+        return LightStats(self)
 
     def colour_light_table(self, h, bpc):
         """dav1d_hip_colour_light_table: (q, e) of a handle of `bpc` bits — the light table in fixed point of the linear-light exports, q[v] =

@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["capi.hip", "api_picture.hip", "api_lists.hip", "api_batch.hip", "api_recon.hip", "api_intra.hip", "chunk.hip", "frame.hip", "dsp_table.hip", "dsp_table_post.hip", "itx.hip", "mc.hip", "recon.hip", "intra_pair.hip", "intra_flow.hip", "intra_sb.hip", "lfmask.hip", "refmvs.hip", "peer.hip", "mcx.hip", "comp.hip", "cdef.hip", "loopfilter.hip", "ipred.hip", "lr.hip", "fg.hip", "surface.hip", "surface_grain.hip", "surface_scale.hip", "surface_rgb.hip", "surface_colour.hip", "surface_rgb_scale.hip", "surface_batch.hip", "surface_resize.hip", "surface_reduce.hip", "surface_colour_reduce.hip", "surface_linear.hip"]
+SOURCES = ["capi.hip", "api_picture.hip", "api_lists.hip", "api_batch.hip", "api_recon.hip", "api_intra.hip", "chunk.hip", "frame.hip", "dsp_table.hip", "dsp_table_post.hip", "itx.hip", "mc.hip", "recon.hip", "intra_pair.hip", "intra_flow.hip", "intra_sb.hip", "lfmask.hip", "refmvs.hip", "peer.hip", "mcx.hip", "comp.hip", "cdef.hip", "loopfilter.hip", "ipred.hip", "lr.hip", "fg.hip", "surface.hip", "surface_grain.hip", "surface_scale.hip", "surface_rgb.hip", "surface_colour.hip", "surface_rgb_scale.hip", "surface_batch.hip", "surface_resize.hip", "surface_reduce.hip", "surface_colour_reduce.hip", "surface_linear.hip", "surface_stats.hip"]
 # host side of the pass-2 hand-off: plain C99 (the lister, its AV1 geometry), compiled with gcc
 HOST_SOURCES = ["av1_host.c", "lister.c", "filter_lister.c", "lf_rects.c"]
 HOST = os.path.join(HERE, "host")

@@ -631,6 +631,68 @@ DAV1D_HIP_API int dav1d_hip_surface_export_rgb_linear_reduced_batch(Dav1dHipCont
                                                                     const Dav1dHipColour *colour, int filter, int *bad_item /* may be NULL */);
 DAV1D_HIP_API int dav1d_hip_surface_rgb_linear_rows_needed(const Dav1dHipSurface *dst, const Dav1dHipPicture *src, const Dav1dHipSurfaceRect *crop,
                                                            const Dav1dHipRgbParams *params, int filter, int drow1);
+/* Per-picture light statistics on the device (dav1d_amd/csrc/surface_stats.hip): a histogram of the luminance of a picture over the
+ * index of a toned handle's gain, for a tone peak that follows the content — the caller reads it, picks a peak, makes a gain and hands it to
+ * dav1d_hip_colour_update_tone below.  Every count is an integer: exact, independent of the order of the adds, additive over bands, crops and pictures.
+ * Definition.  W is the crop window of src taken as a picture of its own; the windows and the crop rule are those of
+ * dav1d_hip_surface_export_rgb_linear_reduced (even x0 / y0 on a subsampled axis; no sample outside the crop takes part).  (R, G, B)(x, y) are the
+ * integers dav1d_hip_surface_export_rgb computes for W at its own size; matrix, full_range and chroma_pos mean what they mean in Dav1dHipSurface and
+ * Dav1dHipRgbParams, the I400 and matrix-0 rules included.  l_c = lin[code_c] of the handle (the code masked into the table, as in every colour-managed
+ * export).  Y, x and h are step 1b's of the tone part above, word for word: p_j = k[j] * l_j, Y = (p_0 + p_1) + p_2 in float32 with five roundings and
+ * nothing fused; x = Y > 0 ? (Y < 1 ? Y : 1) : 0; h = the binary16 bit pattern of x, ties to even, subnormals kept, 0 <= h <= 0x3C00.  k is the
+ * CALL's: a tone part the handle may carry is ignored (a caller cannot have the handle's k before it has a peak, and the statistics must not depend
+ * on the curve they feed).  For every pixel of luma rows [row0, row1) of W:
+ *     hist[h] += 1, n += 1, n_above += (Y > 1.0f), n_nonpos += !(Y > 0.0f), max_light = max(max_light, l_R, l_G, l_B)
+ * (lin is finite — dav1d_hip_colour_create refuses any other — so the maximum has no order problem; of -0.0 and +0 it keeps +0).
+ * Calls accumulate until dav1d_hip_light_stats_reset.  Rows follow the family's band rule — clamped to W, row0 / row1 even on a layout that subsamples
+ * rows unless row1 is W's end — so the bands of a picture add up to the picture and a band can be counted as soon as row progress has published it:
+ * the rows a band needs are crop.y0 + what dav1d_hip_surface_rgb_rows_needed promises for the same rows of W.  An empty row range counts nothing
+ * and is 0.
+ * The accumulator is memory of the context's device and, like a colour handle, serves one context at a time; dav1d_hip_light_stats_alive is the
+ * number of them alive (dav1d_hip_live_objects has room for its four kinds only).  dav1d_hip_light_stats_create gives a zeroed one (n == 0,
+ * max_light == -INFINITY); _reset zeroes it on the context's stream without waiting; _destroy waits for the context's stream; _read waits for it
+ * and copies.  dav1d_hip_picture_light_stats is asynchronous like the exports: ONE launch on the context's stream, between the events
+ * dav1d_hip_last_kernel_ms reads, of at most 512 workgroups whatever the size (more only where a workgroup's share would reach 2^32 pixels, which no picture that fits memory does); no allocation, no host wait, no staging; src is const and a
+ * DAV1D_HIP_TWIN_ONLY picture stays one.  Raster, both-valid and twin-only pictures, 8 / 10 / 12 bits, all four layouts.
+ * Errors of dav1d_hip_picture_light_stats, before anything is enqueued, in this order: -EINVAL for a NULL c, s, src, colour or k; what
+ * dav1d_hip_surface_export_rgb_linear_reduced refuses about the picture, the crop, the matrix and chroma_pos and the rows, with its codes and in its
+ * order; -EINVAL for a k entry that is not finite; -EINVAL for a handle whose bpc is not the picture's; -EXDEV for a picture, then a handle, then an
+ * accumulator of another device.  _reset and _read: -EINVAL for a NULL argument, -EXDEV for an accumulator of another device.
+ * The host helpers use integers but for one documented sum.  dav1d_hip_light_stats_rank: the smallest h with hist[0] + .. + hist[h] >= rank; -EINVAL
+ * for a NULL argument, rank == 0 or rank > n.  dav1d_hip_light_stats_mean: the sum over ASCENDING h of (double) hist[h] * value(h), value(h) the
+ * number the binary16 pattern h stands for, divided by (double) n; 0 for n == 0 or NULL.  The caller turns a bin into nits by the scale it put into
+ * k: with k = K / 10000, K as in dav1d_hip_colour_tables_toned, on a PQ table whose lin is in nits, bin h is value(h) * 10000 nits; the tables of that
+ * helper count light in a unit of their own (peak_nits with trc_out != 8, white_nits with trc_out == 8), so there k = K unit / 10000.
+ * Out of scope: smoothing the peak over time, scene cuts, a batch form, per-region histograms, chromaticity statistics. */
+typedef struct Dav1dHipLightStats Dav1dHipLightStats;
+typedef struct Dav1dHipLightStatsData {
+    uint64_t n;          /* pixels counted */
+    uint64_t n_above;    /* of them: Y > 1.0f (they are counted in hist[0x3C00] as well) */
+    uint64_t n_nonpos;   /* of them: !(Y > 0), i.e. negative, -0.0, +0 and NaN (counted in hist[0] as well) */
+    float    max_light;  /* largest l_c over all counted pixels and the three channels; -INFINITY while n == 0 */
+    uint64_t hist[DAV1D_HIP_COLOUR_ENC_N];
+} Dav1dHipLightStatsData;
+DAV1D_HIP_API int dav1d_hip_light_stats_create(Dav1dHipContext *c, Dav1dHipLightStats **out);
+DAV1D_HIP_API int dav1d_hip_light_stats_destroy(Dav1dHipContext *c, Dav1dHipLightStats *s);
+DAV1D_HIP_API long long dav1d_hip_light_stats_alive(void);
+DAV1D_HIP_API int dav1d_hip_light_stats_reset(Dav1dHipContext *c, Dav1dHipLightStats *s);
+DAV1D_HIP_API int dav1d_hip_picture_light_stats(Dav1dHipContext *c, Dav1dHipLightStats *s, const Dav1dHipPicture *src,
+                                                const Dav1dHipSurfaceRect *crop /* NULL = everything */, int matrix, int full_range, int chroma_pos,
+                                                const Dav1dHipColour *colour, const float k[3], int row0, int row1);
+DAV1D_HIP_API int dav1d_hip_light_stats_read(Dav1dHipContext *c, const Dav1dHipLightStats *s, Dav1dHipLightStatsData *out);
+DAV1D_HIP_API int dav1d_hip_light_stats_rank(const Dav1dHipLightStatsData *d, uint64_t rank, int *h);
+DAV1D_HIP_API double dav1d_hip_light_stats_mean(const Dav1dHipLightStatsData *d);
+/* Replaces the tone part of a LIVE handle, in stream order: a measured peak changes per scene, and dav1d_hip_colour_create_toned may wait for the
+ * device.  `h` is a handle that HAS a tone part, so its allocation holds a gain already.  The new gain is copied on the context's stream and k is
+ * swapped for the launches enqueued after the call: exports enqueued before the call use the old part, exports enqueued after it the new one, with no
+ * sync in between.  The caller's gain may be freed or overwritten on return: the copy leaves from a slot of the context's staging ring (which waits
+ * only when all of its slots are still in flight).  Nothing is allocated once the ring's slots exist; the handle's LDS, light table in fixed point
+ * and launch shapes stay untouched, and dav1d_hip_live_objects counts what it counted.
+ * Errors, before anything is enqueued or changed: -EINVAL for a NULL argument; -EINVAL for a handle without a tone part; -EINVAL for a NULL gain, a
+ * k entry that is not finite, a gain entry with all exponent bits set; -EXDEV for a handle of another device.  A failure of the runtime itself while the copy
+ * is enqueued (-EIO and the like) is another matter: k stays what it was, but the gain on the device may be partly the new one, and the call is to be
+ * repeated or the handle destroyed. */
+DAV1D_HIP_API int dav1d_hip_colour_update_tone(Dav1dHipContext *c, Dav1dHipColour *h, const Dav1dHipColourTone *t);
 /* host <-> device plane copies; host_stride in bytes; copies the PADDED plane
  * (aligned dimensions) when `padded` is non-zero, else the visible w x h. */
 DAV1D_HIP_API int dav1d_hip_plane_upload(Dav1dHipContext *c, const Dav1dHipPicture *pic, int plane,

@@ -2,7 +2,7 @@
 """Device time of dav1d_hip_surface_export on 8K 4:2:0 10-bit pictures that live in their tiled twin, against the existing kernel that
 does the nearest job, dav1d_hip_picture_untile (twin in, raster planes out), timed by the same loop in the same run on the same pictures.
 
-    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced | --colour-reduced | --linear-reduced | --toned] [--pairs 4] [--calls 200] [--repeats 3]
+    python tools/surface_bench.py [--short] [--grain | --scaled | --rgb | --rgb-scaled | --batch | --colour | --reduced | --colour-reduced | --linear-reduced | --toned | --stats] [--pairs 4] [--calls 200] [--repeats 3]
 
 N source pictures and N surfaces in rotation (a picture plus its surface is about 200 MB: four pairs do not fit the 256 MiB Infinity
 Cache), 20 warm-up calls, then `calls` timed calls per variant between two HIP events on the context's stream, the variants alternated,
@@ -47,6 +47,8 @@ calls; without a bar, both next to dav1d_hip_surface_export_rgb_colour_reduced a
 --toned: the tone part of a handle (dav1d_hip_colour_create_toned), by the same method: dav1d_hip_surface_export_rgb_colour at full size,
 dav1d_hip_surface_export_rgb_colour_reduced and dav1d_hip_surface_export_rgb_linear_reduced 8K to 224 x 224 and the linear batch of 64, each with the un-toned
 handle of dav1d_hip_colour_tables and with the toned one of dav1d_hip_colour_tables_toned, alternated; the ratio toned / un-toned per call, without a bar.
+--stats: dav1d_hip_picture_light_stats of the whole picture on uniform noise, a flat picture and a smooth gradient with a letterbox, against
+dav1d_hip_surface_export_rgb_colour at full size with a lin-only handle into planar float16 in the same run; then the host time of dav1d_hip_colour_update_tone.
 Needs the GPU; there is no fallback."""
 import argparse
 import ctypes as C
@@ -824,6 +826,104 @@ def toned_runs(a, ctx, ev, pics, src_bytes):
     ctx.close()
 
 
+def stats_runs(a, ctx, ev, pics, src_bytes):
+    """per-picture light statistics: dav1d_hip_picture_light_stats of the whole picture on three contents — uniform noise, a flat
+    picture, a smooth gradient with a letterbox — against dav1d_hip_surface_export_rgb_colour of the noise pictures at full size with a lin-only handle
+    into planar float16 (the same samples, the same three lookups a pixel, and a surface written on top), alternated within a round; then the host
+    time of dav1d_hip_colour_update_tone with an export right behind it."""
+    w, h, bpc, layout = a.width, a.height, 10, api.LAYOUT_I420
+    rounds, calls = 1 if a.short else max(a.repeats, 10), min(a.calls, 40)
+    lin, m, enc, has_matrix, has_enc, K, gain, has_gain = api.colour_tables_toned(ctx.lib, bpc, 16, 9, 13, 1, 203.0, 1000.0)
+    plain, toned = ctx.colour(lin, bpc=bpc), ctx.colour(lin, m, enc, bpc=bpc, tone=(K, gain))
+    k = (K.astype(np.float64) / 10.0).astype(np.float32)
+    contents = {"noise": pics}
+    for name in ("flat", "gradient + letterbox"):
+        group = []
+        for i in range(a.pairs):
+            p = ctx.picture(w, h, layout, bpc)
+            for pl in range(3):
+                shape = p.padded_shape(pl)
+                if name == "flat":
+                    plane = np.full(shape, (500, 520, 500)[pl] + i, np.uint16)
+                else:
+                    yy, xx = np.arange(shape[0])[:, None], np.arange(shape[1])[None, :]
+                    plane = (64 + (xx * 700 // shape[1] + yy * 100 // shape[0] + i)).astype(np.uint16) if pl == 0 else np.full(shape, 512, np.uint16)
+                    bar = shape[0] // 8          # 2.39:1 in 16:9 leaves about an eighth above and below
+                    plane[:bar] = plane[shape[0] - bar:] = 64 if pl == 0 else 512
+                p.upload(pl, plane)
+            p.retile()
+            p.pic.twin_ok = api.TWIN_ONLY
+            group.append(p)
+        contents[name] = group
+    ctx.sync()
+    fulls = [ctx.surface(w, h, layout, bpc, api.SURFACE_RGB_PLANAR, api.SAMPLE_F16, matrix=9) for _ in range(a.pairs)]
+    stats = ctx.light_stats()
+    runs = [("0. export_rgb_colour to %dx%d planar float16, lin only, noise (yardstick)" % (w, h), src_bytes + 3 * 2 * w * h,
+             lambda i: pics[i % a.pairs].export_rgb_colour(fulls[i % a.pairs], plain, 1))]
+    for name, group in contents.items():
+        runs.append(("1. picture_light_stats, %s" % name, src_bytes, lambda i, group=group: stats.add(group[i % a.pairs], plain, k, matrix=9, chroma_pos=1)))
+    print("# surface_bench --stats on %s: %dx%d 4:2:0 %d-bit twin-only sources, PQ lin, chroma_pos 1, %d pictures in rotation, 3 warm-up + %d timed calls per variant and round, "
+          "%d rounds, the variants alternated within a round" % (socket.gethostname(), w, h, bpc, a.pairs, calls, rounds))
+    print("# bytes per call = bytes read + bytes written, from the shapes (tables not counted); device ms between two events around the timed calls; host ms: the clock around "
+          "issuing them and the sync; last ms: dav1d_hip_last_kernel_ms of the last call")
+    results = {r[0]: [] for r in runs}
+    for rnd in range(rounds):
+        for name, nbytes, call in runs:
+            for i in range(3):
+                call(i)
+            ctx.sync()
+            stats.reset()
+            t0 = time.perf_counter()
+            ev.start()
+            for i in range(calls):
+                call(i)
+            ms = ev.stop_ms() / calls
+            host = (time.perf_counter() - t0) * 1e3 / calls
+            last = ctx.last_kernel_ms()
+            results[name].append((ms, host, last))
+            print("round %2d  %-90s device %8.4f ms/call  host %8.4f  last %8.4f  %7.1f MB/call  %7.0f GB/s" % (rnd, name, ms, host, last, nbytes / 1e6, nbytes / ms / 1e6))
+            if name.startswith("1."):
+                d = stats.read()
+                assert d["n"] == calls * w * h and int(d["hist"].sum()) == d["n"], "every pixel of every call was counted"
+    print("# summary (median [min .. max] over the rounds)")
+    med = {}
+    for name, nbytes, _ in runs:
+        cols = [sorted(v[i] for v in results[name]) for i in range(3)]
+        m3 = [c[len(c) // 2] for c in cols]
+        med[name] = (m3[0], cols[0][-1] - cols[0][0])
+        print("summary   %-90s device %8.4f [%8.4f .. %8.4f]  host %8.4f [%8.4f .. %8.4f]  last %8.4f [%8.4f .. %8.4f] ms   median %7.0f GB/s"
+              % (name, m3[0], cols[0][0], cols[0][-1], m3[1], cols[1][0], cols[1][-1], m3[2], cols[2][0], cols[2][-1], nbytes / m3[0] / 1e6))
+    names = [r[0] for r in runs]
+    print("ratio     stats on noise / yardstick = %.3f (should not exceed 1; the yardstick spreads over %.4f ms)" % (med[names[1]][0] / med[names[0]][0], med[names[0]][1]))
+    print("ratio     stats flat / noise = %.3f; gradient + letterbox / noise = %.3f (the contention handling)" % (med[names[2]][0] / med[names[1]][0], med[names[3]][0] / med[names[1]][0]))
+    # dav1d_hip_colour_update_tone: the host time of the call, an export right behind each
+    n = 40
+    for i in range(4):
+        ctx.colour_update_tone(toned, (K, gain))
+        pics[i % a.pairs].export_rgb_colour(fulls[i % a.pairs], toned, 1)
+    ctx.sync()
+    host_us = []
+    ev.start()
+    for i in range(n):
+        t0 = time.perf_counter()
+        ctx.colour_update_tone(toned, (K, gain))
+        host_us.append((time.perf_counter() - t0) * 1e6)
+        pics[i % a.pairs].export_rgb_colour(fulls[i % a.pairs], toned, 1)
+    ms = ev.stop_ms() / n
+    host_us.sort()
+    print("update    colour_update_tone + export_rgb_colour (toned, planar float16): host time of the update through Python median %.1f us [%.1f .. %.1f]; device %.4f ms per pair "
+          "(the export alone is line 1 of --toned)" % (host_us[n // 2], host_us[0], host_us[-1], ms))
+    stats.free()
+    ctx.colour_destroy(plain)
+    ctx.colour_destroy(toned)
+    for group in contents.values():
+        for p in group:
+            p.free()
+    for s_ in fulls:
+        s_.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true", help="40 calls, one repeat (for a kernel trace)")
@@ -837,6 +937,7 @@ def main():
     ap.add_argument("--colour-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_colour_reduced and its batch against export_rgb_reduced; at 2:1 against export_scaled + export_rgb_colour")
     ap.add_argument("--linear-reduced", action="store_true", help="dav1d_hip_surface_export_rgb_linear_reduced against a full-size export_rgb_colour; its batch against 64 single calls")
     ap.add_argument("--toned", action="store_true", help="the three colour-managed single calls and the linear batch of 64 with an un-toned and a toned handle, alternated")
+    ap.add_argument("--stats", action="store_true", help="dav1d_hip_picture_light_stats on noise, a flat picture and a gradient with a letterbox against a full-size export_rgb_colour; update_tone's host time")
     ap.add_argument("--cells", type=lambda v: [int(x) for x in v.split(",") if x], default=[], help="--colour: variants (a) and (c) again with these values of the option colour_cells")
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--calls", type=int, default=200)
@@ -889,6 +990,8 @@ def main():
         return linear_reduced_runs(a, ctx, ev, pics, src_bytes)
     if a.toned:
         return toned_runs(a, ctx, ev, pics, src_bytes)
+    if a.stats:
+        return stats_runs(a, ctx, ev, pics, src_bytes)
     runs = []
     for name, fmt, sample, out_bytes in variants:
         surfs = [ctx.surface(w, h, layout, bpc, fmt, sample) for _ in range(a.pairs)]
